@@ -16,7 +16,17 @@ spawns the N rank processes itself (before any GPU call); under torchrun it read
 Model weights are a seeded synthetic GGML file of the named architecture (no checkpoints offline);
 audio is synthetic (tools/make_model.synthetic_pcm, seed 1234 + global chunk index).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times --steps steps and prints the result line (the headline with the
+roofline of its dominant kernel, which is event-timed inside those same steps). Everything that takes
+runs of its own (the CPU baseline, the reference's other workloads, the serving and host-PCM lines, the
+f16 line, the audio front-end, the app's call pattern) is behind --full; each of those legs can still
+be switched on or off by its own option. --dump-outputs DIR writes what the last timed step returned
+(every decoded token and segment of every chunk) as .npy arrays, for comparing two builds.
+
+The model file is looked up in --model-dir (default: .nw_models/ beside this file, where
+__graft_entry__.build() writes the default model once) and written there when missing.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -44,6 +54,10 @@ FP8_PEAK_TFS = 5000.0        # dense fp8 MFMA peak
 # PMC traffic pass of the roofline kernel (tools/pmc.sh -> tools/pmc_traffic.py), chosen by name
 PMC_TRAFFIC_FILE = "r06_pmc_traffic.json"
 KT_LAYER_STRIDE = 8
+# where the synthetic model files are kept between runs (NW_MODEL_DIR overrides it)
+MODEL_DIR = os.environ.get("NW_MODEL_DIR") or os.path.join(ROOT, ".nw_models")
+# the legs behind --full, with the value each has there (0 in a plain run unless its own option is given)
+FULL_LEGS = dict(variants=1, inflight_line=1, f16_line=1, frontend=1, app_pattern=1, cpu_baseline=1)
 
 
 def log(*a):
@@ -72,6 +86,51 @@ def ensure_model(path: str, shape: str):
 
         write_model(path, shape, 0, progress=progress)
         log(f"[bench] wrote synthetic {shape} model to {path} in {time.time() - t:.1f}s")
+
+
+def model_shape(model: str = "large-v3", weights: str = "conf", quant: str = "none") -> str:
+    """tools/make_model.py's name of the synthetic model that --model / --weights / --quant select."""
+    return model + ("+conf" if weights == "conf" else "") + ("" if quant == "none" else "+" + quant)
+
+
+def prepare_default_model() -> str:
+    """Write the default run's model file once (__graft_entry__.build() calls this, so that a
+    benchmark run does not spend its first 15 s writing 3 GB)."""
+    os.makedirs(MODEL_DIR, exist_ok=True)
+    path = os.path.join(MODEL_DIR, f"{model_shape()}_s0.bin")
+    ensure_model(path, model_shape())
+    return path
+
+
+def start_chunks(ids: list[int]) -> list:
+    """Futures of the synthetic 30 s chunks of these global indices, in order. Each chunk is seeded by its
+    index alone, so a few threads synthesise them side by side (numpy releases the GIL in the array
+    work) while the caller loads the model."""
+    from concurrent.futures import ThreadPoolExecutor
+    from make_model import synthetic_pcm
+    ex = ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0)))))
+    futs = [ex.submit(synthetic_pcm, cid) for cid in ids]
+    ex.shutdown(wait=False)
+    return futs
+
+
+def collect_outputs(st, ids: list[int]) -> dict:
+    """What the caller of the last full_batch receives, as arrays: one row per decoded token
+    (global chunk index, segment, position in the segment, id, tid, p, plog, pt, ptsum) and one row
+    per segment (global chunk index, segment, t0, t1, number of tokens). float64 holds all of them
+    exactly."""
+    import numpy as np
+    L = st.L
+    toks, segs = [], []
+    for j, cid in enumerate(ids):
+        for s in range(L.whisper_mi355x_batch_n_segments(st.ptr, j)):
+            nt = L.whisper_mi355x_batch_segment_n_tokens(st.ptr, j, s)
+            segs.append((cid, s, L.whisper_mi355x_batch_segment_t0(st.ptr, j, s),
+                         L.whisper_mi355x_batch_segment_t1(st.ptr, j, s), nt))
+            for t in range(nt):
+                d = L.whisper_mi355x_batch_token_data(st.ptr, j, s, t)
+                toks.append((cid, s, t, d.id, d.tid, d.p, d.plog, d.pt, d.ptsum))
+    return dict(tokens=np.array(toks, np.float64).reshape(-1, 9), segments=np.array(segs, np.float64).reshape(-1, 5))
 
 
 def cgroup_cpus():
@@ -379,7 +438,7 @@ def _wall(fn) -> float:
     return time.perf_counter() - t
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -390,19 +449,19 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "fp8"],
                     help="fp8: bf16 with the encoder QKV/FC1/FC2 GEMMs on e4m3 weights + activations")
     ap.add_argument("--tokens", type=int, default=128, help="decode tokens per chunk (fixed-work mode)")
-    ap.add_argument("--variants", type=int, default=1,
+    ap.add_argument("--variants", type=int, default=None,
                     help="also time the reference's prompted (default vocabulary) and auto-language workloads")
     ap.add_argument("--variant-steps", type=int, default=3)
-    ap.add_argument("--inflight-line", type=int, default=1,
+    ap.add_argument("--inflight-line", type=int, default=None,
                     help="with --variants: also a serving line with two batches in flight (two states)")
-    ap.add_argument("--f16-line", type=int, default=1,
+    ap.add_argument("--f16-line", type=int, default=None,
                     help="with --dtype bf16: also time the same config with f16 weights (the path exact against the oracle up to its near ties)")
     ap.add_argument("--fallback-line", type=int, default=0,
                     help="also time the reference's verbatim FullParams with temperature fallback (slow on "
                          "untrained weights: most windows fall back to sampled re-decodes)")
-    ap.add_argument("--frontend", type=int, default=1,
+    ap.add_argument("--frontend", type=int, default=None,
                     help="also time the GPU audio front-end (audio.rs VAD chunking + 48 kHz -> 16 kHz resampler)")
-    ap.add_argument("--app-pattern", type=int, default=1,
+    ap.add_argument("--app-pattern", type=int, default=None,
                     help="also time the app's per-call pattern (fresh state per 25 s chunk, whisper.rs:66-148) "
                          "on base f16 and this model in its dtype (rank 0)")
     ap.add_argument("--app-calls", type=int, default=6)
@@ -412,13 +471,30 @@ def main():
     ap.add_argument("--weights", default="conf", choices=["conf", "plain"],
                     help="synthetic weight init: conf = a decoder as peaked as a trained one (tools/make_model.py "
                          "+conf), so real greedy termination happens; plain = i.i.d. random")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=None)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this job may use (affinity, capped by the cgroup cpu.max quota)")
-    ap.add_argument("--model-dir", default=os.environ.get("NW_MODEL_DIR", "/tmp/nw_models"))
+    ap.add_argument("--model-dir", default=MODEL_DIR)
     ap.add_argument("--plan", action="store_true",
                     help="CPU dry run of the rank layout: gloo group, shard map and max-over-ranks, no GPU")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: " + ", ".join("--" + k.replace("_", "-") for k in FULL_LEGS)
+                         + " (each 1 here and 0 in a plain run, unless given)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (tokens.npy: one row per decoded token; segments.npy: "
+                         "one row per segment; float64) into DIR")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    for k, v in FULL_LEGS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else 0)
+    return args
+
+
+def main():
+    t_main = time.time()
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -442,8 +518,15 @@ def main():
 
     wrs = load_wrs()
     os.makedirs(args.model_dir, exist_ok=True)
-    shape = args.model + ("+conf" if args.weights == "conf" else "") + ("" if args.quant == "none" else "+" + args.quant)
+    shape = model_shape(args.model, args.weights, args.quant)
     model_path = os.path.join(args.model_dir, f"{shape}_s0.bin")
+    if args.batch > 0:
+        ids = [rank * args.batch + i for i in range(args.batch)]
+        global_batch = args.batch * world
+    else:
+        ids = rank_chunk_ids(rank, world, args.global_batch)
+        global_batch = args.global_batch
+    chunks = start_chunks(ids)  # synthesised while the model loads
     if local_rank == 0:
         ensure_model(model_path, shape)
     barrier()
@@ -471,19 +554,14 @@ def main():
     from make_model import synthetic_pcm
     L = wrs.lib()
     n = 16000 * 30
-    if args.batch > 0:
-        ids = [rank * args.batch + i for i in range(args.batch)]
-        global_batch = args.batch * world
-    else:
-        ids = rank_chunk_ids(rank, world, args.global_batch)
-        global_batch = args.global_batch
     nb = len(ids)
     buf = L.whisper_mi355x_dev_alloc(ctx.ptr, max(1, nb) * n * 4)
     assert buf
-    host = np.empty(n, np.float32)
-    for i, cid in enumerate(ids):
-        host[:] = synthetic_pcm(cid)
+    for i, fut in enumerate(chunks):
+        host = fut.result()
+        assert host.dtype == np.float32 and len(host) == n
         L.whisper_mi355x_memcpy(ctx.ptr, C.c_void_p(buf + i * n * 4), host.ctypes.data, n * 4, 1)
+    del chunks
     jobs = [(buf + i * n * 4, n) for i in range(nb)]
 
     def step(params, fixed=None):
@@ -505,6 +583,8 @@ def main():
     # warmup (untimed) with every kernel class timed once to find the dominant kernel
     L.whisper_mi355x_kernel_timing(st.ptr, 0xFF)
     tw = time.time()
+    if rank == 0:
+        log(f"[bench] set up in {tw - t_main:.1f}s (model load {load_s:.1f}s)")
     for _ in range(args.warmup):
         step(params)
     warm_s = (time.time() - tw) / max(1, args.warmup)
@@ -533,6 +613,10 @@ def main():
     phases = st.phase_ms()
     decoded = L.whisper_mi355x_batch_decoded_tokens(st.ptr)
     L.whisper_mi355x_kernel_timing(st.ptr, 0)
+    if args.dump_outputs:  # before any other leg runs on this state: these are the last timed step's results
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in collect_outputs(st, ids).items():
+            np.save(os.path.join(args.dump_outputs, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), a)
 
     # the reference's own workloads: the app always passes its default vocabulary as
     # the initial prompt (config.rs:40-42, whisper.rs:98-109) with language "auto" (config.rs:49)

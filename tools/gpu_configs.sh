@@ -2,11 +2,12 @@
 # GPU box: bench lines for the secondary BASELINE configs (base f16 B=1, small bf16 B=32,
 # large-v3-turbo bf16 B=256), one GPU each step with its own time limit; a failure ends the run.
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
-cd "$R" && mkdir -p gpurun_out
+OUT="${OUT:-$R/bench_out}"
+cd "$R" && mkdir -p "$OUT"
 run() {
     local tag=$1; shift
-    timeout -k 10 600 python bench.py "$@" > "gpurun_out/cfg_$tag.json" 2> "gpurun_out/cfg_$tag.err"
-    local rc=$?; echo "$tag rc=$rc"; cat "gpurun_out/cfg_$tag.json"
+    timeout -k 10 600 python bench.py --full "$@" > "$OUT/cfg_$tag.json" 2> "$OUT/cfg_$tag.err"
+    local rc=$?; echo "$tag rc=$rc"; cat "$OUT/cfg_$tag.json"
     return $rc
 }
 run base_f16_b1 --model base --dtype f16 --batch 1 --steps 3 --warmup 1 &&
