@@ -71,11 +71,9 @@ WHISPER_API long whisper_mi355x_batch_decoded_tokens(struct whisper_state * stat
 /* tokens generated by every whisper_full / whisper_mi355x_full_batch call of the process so far (lets a
  * caller that drives whisper.h through its own states, e.g. the WhisperEngine mirror, count per call) */
 WHISPER_API long whisper_mi355x_decoded_tokens_total(void);
-/* Debug: the batched persistent decoder chain's hand-off counters and error word after the state's last
- * decode step (u32 words, out must hold them); returns the word count (-count if cap is too small). */
-/* Debug: device pointers of a state's decode workspace (0 residual x, 1 final LayerNorm rows, 2 q|k|v rows of
- * the batched chain, 3 attention outputs, 4 GELU rows, 5 cross q, 6 Q', 7 cross-attention partials, 8 their
- * {m, l}); NULL when not allocated. */
+/* Debug: device pointers of a state's decode workspace (0 residual x, 1 final LayerNorm rows, 2 unused (NULL),
+ * 3 attention outputs, 4 GELU rows, 5 cross q, 6 Q', 7 cross-attention partials, 8 their {m, l}); NULL when
+ * not allocated. */
 WHISPER_API void * whisper_mi355x_debug_ws(struct whisper_state * state, int which);
 
 /* Per-window decisions of whisper_full's temperature-fallback loop (the integer outcomes that are
@@ -105,6 +103,20 @@ WHISPER_API int whisper_mi355x_window_decisions(struct whisper_state * state, in
  * stream-synchronised phases): mel, encode (incl. cross-KV), prefill, decode steps, logits. */
 WHISPER_API int whisper_mi355x_phase_ms(struct whisper_state * state, double out[5]);
 
+/* Token-level timestamps from cross-attention DTW (whisper_context_params.dtw_token_timestamps with an
+ * alignment-heads preset, dtw_n_top or dtw_aheads; DESIGN.md "Token timestamps (DTW)"). Every text token of an
+ * aligned window carries whisper_token_data.t_dtw (10 ms units, as t0 / t1) through whisper_full_get_token_data*
+ * and whisper_mi355x_batch_token_data; every other token has t_dtw = -1. An invalid configuration (preset NONE,
+ * an empty list, dtw_n_top outside [1, n_text_layer], a head outside the model) makes the init return NULL.
+ * whisper_mi355x_align_ms: wall time of the alignment passes of the last full / full_batch call (0 with the
+ * switch off; not part of whisper_mi355x_phase_ms' five slots).
+ * whisper_mi355x_align_cost: the cost matrix [rows][frames] (f32; rows = the `not` row + the text tokens) of the
+ * job's last aligned window, copied from the device buffer the DTW kernel read. *rows = 0 when no window of the
+ * job was aligned. Returns 0, -1 on bad arguments, -2 when cap_floats is too small (rows / frames are set). */
+WHISPER_API double whisper_mi355x_align_ms(struct whisper_state * state);
+WHISPER_API int whisper_mi355x_align_cost(struct whisper_state * state, int job, float * out, long cap_floats,
+                                          int * rows, int * frames);
+
 /* Normalised log-mel of the last whisper_pcm_to_mel_with_state / whisper_full_with_state call,
  * copied to host: [n_mel][n_len] f32. Returns n_len. */
 WHISPER_API int whisper_mi355x_get_mel(struct whisper_state * state, float * out, int cap_floats);
@@ -114,8 +126,9 @@ WHISPER_API int whisper_mi355x_get_encoder_out(struct whisper_state * state, flo
 /* Live per-kernel-class timing with HIP events on the state's stream (used by bench.py for the
  * roofline). Classes: 0 encoder-side GEMM (work = FLOPs), 1 encoder attention (FLOPs),
  * 2 decoder cross-attention (HBM bytes), 3 decoder self-attention (bytes), 4 decoder GEMM (bytes),
- * 5 logits processing (bytes), 6 mel (bytes), 7 the persistent decode step (bytes), 8 the batched
- * persistent decoder chain (bytes). class_mask bit k times class k (0 = off); bits 16..23, when > 1, time
+ * 5 logits processing (bytes), 6 mel (bytes), 7 the persistent decode step (bytes), 8 prefill attention
+ * (bytes), 9 / 10 / 11 the token-timestamp alignment's score (FLOPs), cost (bytes) and DTW (bytes) kernels.
+ * class_mask bit k times class k (0 = off); bits 16..23, when > 1, time
  * the decoder's per-layer attention launches (classes 2, 3) of every k-th layer only.
  * Every call resets the counters; stats out = {total ms, launches, total work}. */
 WHISPER_API int whisper_mi355x_kernel_timing(struct whisper_state * state, int class_mask);
@@ -198,6 +211,29 @@ WHISPER_API int whisper_mi355x_debug_xattn(struct whisper_context * ctx, const v
                                            const void * q, const void * wkt, const void * wv, const float * bv,
                                            int n, int n_ctx, int d, float scale, int splits, float rescale_thr,
                                            void * out, int reps, float * ms);
+
+/* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
+ * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.
+ * scores: q [n_text_layer][sum n_rows][d] (device, compute type: the cross-Q rows of every layer, already scaled
+ * by d_head^-0.25), cross = a cross K/V cache [n_slots][n_text_layer][2][H][n_audio_ctx][64] (device), slot[k] =
+ * the clip's slot, heads {head_layer[a], head_idx[a]} -> P (device f32), clip k at sum_{k' < k} A n_rows F,
+ * laid out [A][n_rows][F]: softmax over all n_audio_ctx keys, frames t < F kept. One launch per layer.
+ * cost: P as above, n_sot[k] leading rows and the last row dropped -> cost (device f32) [N_k][F_k] per clip,
+ * N_k = n_rows[k] - n_sot[k] - 1.
+ * dtw: cost (device f32) [rows[k]][frames[k]] per clip, all clips in one launch -> fr (host int, rows[k] per
+ * clip: first frame of every row), path (host, optional: int pairs {row, frame} from the last cell back to
+ * (0, 0), rows[k] + frames[k] pairs reserved per clip) and path_len (host, optional: pairs written per clip).
+ * host arrays are plain host pointers. Return 0, or -1 on bad arguments. */
+WHISPER_API int whisper_mi355x_debug_align_scores(struct whisper_context * ctx, const void * q, const void * cross,
+                                                  int n_slots, int n_clips, const int * slot, const int * n_rows,
+                                                  const int * frames, int n_heads, const int * head_layer,
+                                                  const int * head_idx, float * P);
+WHISPER_API int whisper_mi355x_debug_align_cost(struct whisper_context * ctx, const float * P, int n_clips,
+                                                const int * n_rows, const int * n_sot, const int * frames, int n_heads,
+                                                float * cost);
+WHISPER_API int whisper_mi355x_debug_align_dtw(struct whisper_context * ctx, const float * cost, int n_clips,
+                                               const int * rows, const int * frames, int * fr, int * path,
+                                               int * path_len);
 
 /* Audio front-end on the GPU (src-tauri/src/audio.rs), for n_clips clips at
  * once on HIP device `device`. pcm / audio / out point at host buffers, or (on_device = true) at

@@ -62,6 +62,11 @@ static whisper_context* make_ctx(const char* path, whisper_context_params cp, in
         fprintf(stderr, "whisper_mi355x: fp8 mode needs an f16 model file; %s is block-quantized, fp8 off\n", path);
         w->c.fp8_enc = false;
     }
+    if (!resolve_dtw(&w->c, cp)) {  // (one stderr line said why)
+        free_context(&w->c);
+        delete w;
+        return nullptr;
+    }
     w->c.owner = w;
     return w;
 }
@@ -389,7 +394,7 @@ static whisper_token_data tdata(const Segment* g, int t) {
     if (!g || t < 0 || t >= (int)g->tokens.size()) { r.id = -1; return r; }
     const TokenData& x = g->tokens[t];
     r.id = x.id; r.tid = x.tid; r.p = x.p; r.plog = x.plog; r.pt = x.pt; r.ptsum = x.ptsum;
-    r.t0 = -1; r.t1 = -1; r.t_dtw = -1; r.vlen = 0.0f;
+    r.t0 = -1; r.t1 = -1; r.t_dtw = x.t_dtw; r.vlen = 0.0f;
     return r;
 }
 whisper_token_data whisper_full_get_token_data_from_state(struct whisper_state* s, int i, int t) { return tdata(seg(s, 0, i), t); }
@@ -493,6 +498,21 @@ int whisper_mi355x_phase_ms(struct whisper_state* s, double out[5]) {
     if (!s) return -1;
     for (int i = 0; i < 5; i++) out[i] = s->phase_ms[i];
     return 0;
+}
+double whisper_mi355x_align_ms(struct whisper_state* s) { return s ? s->align_ms : 0.0; }
+int whisper_mi355x_align_cost(struct whisper_state* s, int job, float* out, long cap, int* rows, int* frames) {
+    return guarded(nullptr, [&]() -> int {
+        if (!s || job < 0 || job >= (int)s->align_info.size()) return -1;
+        const whisper_state::AlignInfo& a = s->align_info[job];
+        if (rows) *rows = a.rows;
+        if (frames) *frames = a.frames;
+        if (a.rows <= 0 || !a.cost) return 0;
+        const long n = (long)a.rows * a.frames;
+        if (!out || cap < n) return -2;
+        hipSetDevice(s->device);
+        WM_CHECK(hipMemcpy(out, a.cost, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    });
 }
 int whisper_mi355x_get_mel(struct whisper_state* s, float* out, int cap) {
     return guarded(nullptr, [&]() -> int {
@@ -823,6 +843,131 @@ int whisper_mi355x_debug_xattn(struct whisper_context* ctx, const void* enc, con
         hipFree(qx);
         hipFree(op);
         hipFree(ml);
+        return 0;
+    });
+}
+
+// ---- token-timestamp alignment kernels (kernels/align.hip) on caller data ------------------------------
+// clip descriptors with the packed offsets the three hooks share: P [A][n_rows][F], cost [N][F], fr [N],
+// path [N + F] pairs, clip after clip
+static std::vector<AlignClip> align_hook_clips(int n_clips, const int* slot, const int* n_rows, const int* n_sot,
+                                               const int* frames, int A, int* max_rows, int* max_n, int* max_f) {
+    std::vector<AlignClip> cl(n_clips);
+    long row0 = 0, p = 0, stt = 0, cost = 0, fr = 0, path = 0;
+    *max_rows = *max_n = *max_f = 0;
+    for (int k = 0; k < n_clips; k++) {
+        AlignClip& a = cl[k];
+        a = AlignClip{};
+        a.slot = slot ? slot[k] : 0; a.row0 = (int)row0; a.n_rows = n_rows[k]; a.n_sot = n_sot ? n_sot[k] : 0; a.frames = frames[k];
+        const long N = a.n_rows - a.n_sot - 1;
+        a.p_off = p; a.st_off = stt; a.cost_off = cost; a.tr_off = cost; a.fr_off = fr; a.path_off = path;
+        row0 += a.n_rows;
+        p += (long)A * a.n_rows * a.frames;
+        stt += (long)A * a.frames * 2;
+        cost += std::max(N, 0L) * a.frames;
+        fr += std::max(N, 0L);
+        path += std::max(N, 0L) + a.frames;
+        *max_rows = std::max(*max_rows, a.n_rows);
+        *max_n = std::max(*max_n, (int)N);
+        *max_f = std::max(*max_f, a.frames);
+    }
+    return cl;
+}
+static AlignClip* align_hook_upload(const std::vector<AlignClip>& cl) {
+    AlignClip* d = nullptr;
+    WM_CHECK(hipMalloc((void**)&d, cl.size() * sizeof(AlignClip)));
+    WM_CHECK(hipMemcpy(d, cl.data(), cl.size() * sizeof(AlignClip), hipMemcpyHostToDevice));
+    return d;
+}
+int whisper_mi355x_debug_align_scores(struct whisper_context* ctx, const void* q, const void* cross, int n_slots,
+                                      int n_clips, const int* slot, const int* n_rows, const int* frames, int n_heads,
+                                      const int* head_layer, const int* head_idx, float* P) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || n_clips <= 0 || n_heads <= 0) return -1;
+        const Hparams& hp = ctx->c.hp;
+        const int L = hp.n_text_layer, H = hp.n_text_head, d = hp.n_text_state;
+        long tot = 0;
+        for (int k = 0; k < n_clips; k++) {
+            if (n_rows[k] < 1 || n_rows[k] > 256 || frames[k] < 1 || frames[k] > hp.n_audio_ctx || slot[k] < 0 ||
+                slot[k] >= n_slots)
+                return -1;
+            tot += n_rows[k];
+        }
+        for (int a = 0; a < n_heads; a++)
+            if (head_layer[a] < 0 || head_layer[a] >= L || head_idx[a] < 0 || head_idx[a] >= H) return -1;
+        hipSetDevice(ctx->c.device);
+        int mr, mn, mf;
+        const std::vector<AlignClip> cl = align_hook_clips(n_clips, slot, n_rows, nullptr, frames, n_heads, &mr, &mn, &mf);
+        AlignClip* dcl = align_hook_upload(cl);
+        int2* dh = nullptr;
+        WM_CHECK(hipMalloc((void**)&dh, n_heads * sizeof(int2)));
+        for (int l = 0; l < L; l++) {  // one launch per layer that has heads, as the engine's pass
+            std::vector<int2> hl;
+            for (int a = 0; a < n_heads; a++)
+                if (head_layer[a] == l) hl.push_back(make_int2(head_idx[a], a));
+            if (hl.empty()) continue;
+            WM_CHECK(hipMemcpy(dh, hl.data(), hl.size() * sizeof(int2), hipMemcpyHostToDevice));
+            launch_align_scores(ctx->c.dt, (const char*)q + (size_t)l * tot * d * 2, d, cross, dcl, n_clips, mr, L, l, H,
+                                hp.n_audio_ctx, dh, (int)hl.size(), P, nullptr);
+            WM_CHECK(hipDeviceSynchronize());
+        }
+        hipFree(dh);
+        hipFree(dcl);
+        return 0;
+    });
+}
+int whisper_mi355x_debug_align_cost(struct whisper_context* ctx, const float* P, int n_clips, const int* n_rows,
+                                    const int* n_sot, const int* frames, int n_heads, float* cost) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || n_clips <= 0 || n_heads <= 0) return -1;
+        for (int k = 0; k < n_clips; k++)
+            if (frames[k] < 1 || n_sot[k] < 0 || n_rows[k] - n_sot[k] - 1 < 1) return -1;
+        hipSetDevice(ctx->c.device);
+        int mr, mn, mf;
+        const std::vector<AlignClip> cl = align_hook_clips(n_clips, nullptr, n_rows, n_sot, frames, n_heads, &mr, &mn, &mf);
+        AlignClip* dcl = align_hook_upload(cl);
+        float* stats = nullptr;
+        const long st_el = cl.back().st_off + (long)n_heads * cl.back().frames * 2;
+        WM_CHECK(hipMalloc((void**)&stats, (size_t)st_el * sizeof(float)));
+        launch_align_cost(P, dcl, n_clips, n_heads, mn, mf, stats, cost, nullptr);
+        WM_CHECK(hipDeviceSynchronize());
+        hipFree(stats);
+        hipFree(dcl);
+        return 0;
+    });
+}
+int whisper_mi355x_debug_align_dtw(struct whisper_context* ctx, const float* cost, int n_clips, const int* rows,
+                                   const int* frames, int* fr, int* path, int* path_len) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || n_clips <= 0 || !fr) return -1;
+        std::vector<int> n_rows(n_clips);
+        for (int k = 0; k < n_clips; k++) {
+            if (rows[k] < 1 || rows[k] > 256 || frames[k] < 1) return -1;
+            n_rows[k] = rows[k] + 1;  // (n_sot = 0, the last row dropped: N = rows)
+        }
+        hipSetDevice(ctx->c.device);
+        int mr, mn, mf;
+        const std::vector<AlignClip> cl = align_hook_clips(n_clips, nullptr, n_rows.data(), nullptr, frames, 1, &mr, &mn, &mf);
+        AlignClip* dcl = align_hook_upload(cl);
+        const long n_cost = cl.back().cost_off + (long)rows[n_clips - 1] * frames[n_clips - 1];
+        const long n_fr = cl.back().fr_off + rows[n_clips - 1];
+        const long n_path = cl.back().path_off + rows[n_clips - 1] + frames[n_clips - 1];
+        unsigned char* trace = nullptr;
+        int *dfr = nullptr, *dpath = nullptr, *dlen = nullptr;
+        WM_CHECK(hipMalloc((void**)&trace, (size_t)n_cost));
+        WM_CHECK(hipMalloc((void**)&dfr, (size_t)n_fr * sizeof(int)));
+        WM_CHECK(hipMalloc((void**)&dpath, (size_t)n_path * 2 * sizeof(int)));
+        WM_CHECK(hipMalloc((void**)&dlen, (size_t)n_clips * sizeof(int)));
+        launch_align_dtw(cost, dcl, n_clips, mn, trace, dfr, dpath, dlen, nullptr);
+        WM_CHECK(hipDeviceSynchronize());
+        WM_CHECK(hipMemcpy(fr, dfr, (size_t)n_fr * sizeof(int), hipMemcpyDeviceToHost));
+        if (path) WM_CHECK(hipMemcpy(path, dpath, (size_t)n_path * 2 * sizeof(int), hipMemcpyDeviceToHost));
+        if (path_len) WM_CHECK(hipMemcpy(path_len, dlen, (size_t)n_clips * sizeof(int), hipMemcpyDeviceToHost));
+        hipFree(trace);
+        hipFree(dfr);
+        hipFree(dpath);
+        hipFree(dlen);
+        hipFree(dcl);
         return 0;
     });
 }

@@ -174,6 +174,8 @@ static void reset_for_reuse(whisper_state* s) {
     s->n_len = s->n_len_org = 0;
     s->logits_host.clear();
     for (double& t : s->phase_ms) t = 0;
+    s->align_ms = 0;
+    s->align_info.clear();
     s->decoded_tokens = 0;
     s->last_enc_windows = 0;
     s->mel_ready = false;
@@ -288,7 +290,16 @@ void recover_state(whisper_state* s) {
     s->kpending.clear();
 }
 
+// the token-timestamp alignment's buffers (ensure_align)
+static void free_align(Workspace& w) {
+    dfree(w.al_clips); dfree(w.al_P); dfree(w.al_stats); dfree(w.al_cost); dfree(w.al_trace); dfree(w.al_fr);
+    if (w.h_al) { char* q = w.h_al; w.h_al = nullptr; WM_CHECK(hipHostFree(q)); }
+    w.al_P_elems = 0;
+    w.al_cap = w.al_rows = 0;
+}
+
 static void free_ws(Workspace& w) {
+    free_align(w);
     // sub-allocations (pos/slot/.. of tok, win_seek/win_slot of win_job, pcm_ptrs/n_* of mel_ptrs)
     // are freed with their parent
     dfree(w.mel_img); dfree(w.h1); dfree(w.hn); dfree(w.qkv); dfree(w.att); dfree(w.ff); dfree(w.x);
@@ -393,6 +404,8 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs) {
         dfree(w.cross); dfree(w.self); dfree(w.dx); dfree(w.dh); dfree(w.dq); dfree(w.datt); dfree(w.dff);
         dfree(w.lrow); dfree(w.logits); dfree(w.probs); dfree(w.tok); dfree(w.ctl); dfree(w.tout); dfree(w.lrec); dfree(w.mel_ptrs);
         dfree(w.splitk); dfree(w.enc); dfree(w.qx); dfree(w.xo); dfree(w.xml); dfree(w.kvslot); dfree(w.qtiles);
+        free_align(w);  // sized by cap_jobs
+        for (auto& a : s->align_info) a = {};  // (pointers into al_cost)
         if (w.h_ring) { WM_CHECK(hipHostFree(w.h_ring)); w.h_ring = nullptr; w.ring = nullptr; }
         for (void** h : {(void**)&w.h_qtiles, (void**)&w.h_ints, (void**)&w.h_tout, (void**)&w.h_ctl})
             if (*h) { void* q = *h; *h = nullptr; WM_CHECK(hipHostFree(q)); }
@@ -1067,8 +1080,17 @@ static void decoder_rows_small(Context* c, whisper_state* s, const DecView& v, b
 // (decode steps: one token per clip, logits for every row, <= 128 rows per view): every LayerNorm
 // is folded into the embedding or into the split-K reduce of the preceding residual GEMM.
 // Otherwise (prefill, one view at r0 = 0) logits of n_rows rows (row r = token lrows[r]).
+// `al` (the token-timestamp alignment, align_windows): the unfused cache-form pass; after the cross-Q GEMM of a
+// layer that has alignment heads the score kernel runs on those rows, and the pass ends after the cross-Q of
+// the highest such layer (the remaining layers, the final LN and the logits GEMM are not needed).
+struct AlignPass {
+    const AlignClip* clips;
+    int n_clips, max_rows;
+    long total_rows;
+    float* P;
+};
 static void decoder_rows(Context* c, whisper_state* s, const DecView& v, int n_rows, bool fused, bool xdirect,
-                         double self_share) {
+                         double self_share, const AlignPass* al = nullptr) {
     const Hparams& hp = c->hp;
     Workspace& w = s->ws;
     const int d = hp.n_text_state, H = hp.n_text_head, V = hp.n_vocab, L = hp.n_text_layer;
@@ -1191,6 +1213,15 @@ static void decoder_rows(Context* c, whisper_state* s, const DecView& v, int n_r
             GemmArgs g = gemm_plain(dh, n_tok, d, Lw.wxq, d, Lw.bxq, dq, d);
             g.scale = c->k_scale; g.sc_div = d; g.sc_mod = 1; g.sc_lim = 1;
             gemm(KCLS, EPI_STORE, g);
+            if (al) {
+                const int k0 = c->dtw_layer_first[l], k1 = c->dtw_layer_first[l + 1];
+                if (k1 > k0) {
+                    KT kt(s, K_ALIGN_SCORES, 2.0 * al->total_rows * hp.n_audio_ctx * 64 * (k1 - k0), st);
+                    launch_align_scores(dt, dq, d, w.cross, al->clips, al->n_clips, al->max_rows, L, l, H, hp.n_audio_ctx,
+                                        (const int2*)c->dtw_heads_dev + k0, k1 - k0, al->P, st);
+                }
+                if (l == c->dtw_last_layer) return;
+            }
             KT kt(s, K_OTHER, (double)n_tok * hp.n_audio_ctx * kvrow, st);
             launch_attn_prefill(dt, dq, d, w.cross, slot, nkv_cross, w.qtiles, w.n_qtiles, L, l, H, hp.n_audio_ctx, d, datt, st);
         }
@@ -1353,6 +1384,11 @@ struct Job {
     int n_new_segments = 0;
     whisper_mi355x_window_decision dec{};                // the current window's fallback decisions
     std::vector<whisper_mi355x_window_decision> decisions;
+    // token-timestamp alignment of the window that just finished (finish_window -> align_windows): its seek and
+    // frame count before seek advanced, and its first new segment
+    bool al_pending = false;
+    int al_seek = 0, al_frames = 0;
+    size_t al_seg0 = 0;
 };
 
 struct Sched {
@@ -1365,7 +1401,7 @@ struct Sched {
     bool single_api;
     int n_max_steps;
     long decoded = 0;
-    double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0;
+    double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0;
 };
 
 static double now_ms() {
@@ -1468,6 +1504,12 @@ static void finish_window(Sched& S, Job& j) {
         }
     }
     j.n_new_segments = (int)(j.result.size() - n_before);
+    if (S.c->dtw && j.n_new_segments > 0) {  // aligned by align_windows before the clip's next encode
+        j.al_pending = true;
+        j.al_seek = j.seek;
+        j.al_frames = std::min(std::min(3000, seek_delta), j.seek_end - j.seek);
+        j.al_seg0 = n_before;
+    }
     j.dec.seek = j.seek;
     j.dec.temp_idx = j.temp_idx;
     j.dec.no_speech = is_no_speech;
@@ -1500,6 +1542,221 @@ static void attempt_done(Sched& S, Job& j) {
         return;
     }
     finish_window(S, j);
+}
+
+
+// ---- token timestamps from cross-attention DTW ------------------------------------------------------
+// (DESIGN.md "Token timestamps (DTW)"; the algorithm is whisper.cpp's
+// whisper_exp_compute_token_level_timestamps_dtw / OpenAI's timing.py)
+static const whisper_ahead kAhTinyEn[] = {{1, 0}, {2, 0}, {2, 5}, {3, 0}, {3, 1}, {3, 2}, {3, 3}, {3, 4}};
+static const whisper_ahead kAhTiny[] = {{2, 2}, {3, 0}, {3, 2}, {3, 3}, {3, 4}, {3, 5}};
+static const whisper_ahead kAhBaseEn[] = {{3, 3}, {4, 7}, {5, 1}, {5, 5}, {5, 7}};
+static const whisper_ahead kAhBase[] = {{3, 1}, {4, 2}, {4, 3}, {4, 7}, {5, 1}, {5, 2}, {5, 4}, {5, 6}};
+static const whisper_ahead kAhSmallEn[] = {{6, 6}, {7, 0}, {7, 3}, {7, 8}, {8, 2}, {8, 5}, {8, 7}, {9, 0}, {9, 4}, {9, 8},
+                                           {9, 10}, {10, 0}, {10, 1}, {10, 2}, {10, 3}, {10, 6}, {10, 11}, {11, 2}, {11, 4}};
+static const whisper_ahead kAhSmall[] = {{5, 3}, {5, 9}, {8, 0}, {8, 4}, {8, 7}, {8, 8}, {9, 0}, {9, 7}, {9, 9}, {10, 5}};
+static const whisper_ahead kAhMediumEn[] = {{11, 4}, {14, 1}, {14, 12}, {14, 14}, {15, 4}, {16, 0}, {16, 4}, {16, 9}, {17, 12},
+                                            {17, 14}, {18, 7}, {18, 10}, {18, 15}, {20, 0}, {20, 3}, {20, 9}, {20, 14}, {21, 12}};
+static const whisper_ahead kAhMedium[] = {{13, 15}, {15, 4}, {15, 15}, {16, 1}, {20, 0}, {23, 4}};
+static const whisper_ahead kAhLargeV1[] = {{9, 19}, {11, 2}, {11, 4}, {11, 17}, {22, 7}, {22, 11}, {22, 17}, {23, 2}, {23, 15}};
+static const whisper_ahead kAhLargeV2[] = {{10, 12}, {13, 17}, {16, 11}, {16, 12}, {16, 13}, {17, 15}, {17, 16}, {18, 4},
+                                           {18, 11}, {18, 19}, {19, 11}, {21, 2}, {21, 3}, {22, 3}, {22, 9}, {22, 12},
+                                           {23, 5}, {23, 7}, {23, 13}, {25, 5}, {26, 1}, {26, 12}, {27, 15}};
+static const whisper_ahead kAhLargeV3[] = {{7, 0}, {10, 17}, {12, 18}, {13, 12}, {16, 1}, {17, 14}, {19, 11}, {21, 4}, {24, 1}, {25, 6}};
+static const whisper_ahead kAhLargeV3Turbo[] = {{2, 4}, {2, 11}, {3, 3}, {3, 6}, {3, 11}, {3, 14}};
+
+bool resolve_dtw(Context* c, const whisper_context_params& cp) {
+    c->dtw = false;
+    c->dtw_heads.clear();
+    if (!cp.dtw_token_timestamps) return true;
+    const int L = c->hp.n_text_layer, H = c->hp.n_text_head;
+    auto bad = [](const char* what) {
+        fprintf(stderr, "whisper_mi355x: dtw_token_timestamps: %s\n", what);
+        return false;
+    };
+    const whisper_ahead* tab = nullptr;
+    size_t n = 0;
+#define WM_AH(name) tab = name, n = sizeof(name) / sizeof(name[0])
+    switch (cp.dtw_aheads_preset) {
+        case WHISPER_AHEADS_NONE: return bad("no alignment heads preset (WHISPER_AHEADS_NONE)");
+        case WHISPER_AHEADS_N_TOP_MOST:
+            if (cp.dtw_n_top < 1 || cp.dtw_n_top > L) return bad("dtw_n_top outside [1, n_text_layer]");
+            for (int l = L - cp.dtw_n_top; l < L; l++)
+                for (int h = 0; h < H; h++) c->dtw_heads.emplace_back(l, h);
+            break;
+        case WHISPER_AHEADS_CUSTOM: tab = cp.dtw_aheads.heads; n = tab ? cp.dtw_aheads.n_heads : 0; break;
+        case WHISPER_AHEADS_TINY_EN: WM_AH(kAhTinyEn); break;
+        case WHISPER_AHEADS_TINY: WM_AH(kAhTiny); break;
+        case WHISPER_AHEADS_BASE_EN: WM_AH(kAhBaseEn); break;
+        case WHISPER_AHEADS_BASE: WM_AH(kAhBase); break;
+        case WHISPER_AHEADS_SMALL_EN: WM_AH(kAhSmallEn); break;
+        case WHISPER_AHEADS_SMALL: WM_AH(kAhSmall); break;
+        case WHISPER_AHEADS_MEDIUM_EN: WM_AH(kAhMediumEn); break;
+        case WHISPER_AHEADS_MEDIUM: WM_AH(kAhMedium); break;
+        case WHISPER_AHEADS_LARGE_V1: WM_AH(kAhLargeV1); break;
+        case WHISPER_AHEADS_LARGE_V2: WM_AH(kAhLargeV2); break;
+        case WHISPER_AHEADS_LARGE_V3: WM_AH(kAhLargeV3); break;
+        case WHISPER_AHEADS_LARGE_V3_TURBO: WM_AH(kAhLargeV3Turbo); break;
+        default: return bad("unknown alignment heads preset");
+    }
+#undef WM_AH
+    for (size_t k = 0; k < n; k++) c->dtw_heads.emplace_back(tab[k].n_text_layer, tab[k].n_head);
+    if (c->dtw_heads.empty()) return bad("empty alignment head list");
+    for (auto& lh : c->dtw_heads)
+        if (lh.first < 0 || lh.first >= L || lh.second < 0 || lh.second >= H) {
+            c->dtw_heads.clear();
+            return bad("an alignment head lies outside the model's n_text_layer x n_text_head");
+        }
+    // the score kernel runs once per layer: the list grouped by layer, each entry with its list index
+    c->dtw_layer_first.assign(L + 1, 0);
+    c->dtw_last_layer = -1;
+    for (auto& lh : c->dtw_heads) {
+        c->dtw_layer_first[lh.first + 1]++;
+        c->dtw_last_layer = std::max(c->dtw_last_layer, lh.first);
+    }
+    for (int l = 0; l < L; l++) c->dtw_layer_first[l + 1] += c->dtw_layer_first[l];
+    c->dtw = true;
+    return true;
+}
+
+// score rows of one group of clips: at most this many bytes of P (a clip of 224 rows x 1500 frames is 1.3 MB
+// per head; large-v3's 10 heads at 128 clips of ~130 rows: 1.0 GB)
+static const size_t kAlignPBytes = (size_t)1 << 30;
+
+static void ensure_align(Context* c, whisper_state* s) {
+    Workspace& w = s->ws;
+    {
+        std::lock_guard<std::mutex> lk(c->dtw_mu);
+        if (!c->dtw_heads_dev) {
+            std::vector<int2> h(c->dtw_heads.size());
+            std::vector<int> at(c->dtw_layer_first.begin(), c->dtw_layer_first.end() - 1);
+            for (size_t a = 0; a < c->dtw_heads.size(); a++) h[at[c->dtw_heads[a].first]++] = make_int2(c->dtw_heads[a].second, (int)a);
+            void* p = nullptr;
+            WM_CHECK(hipMalloc(&p, h.size() * sizeof(int2)));
+            WM_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
+            c->dtw_heads_dev = p;
+        }
+    }
+    if (w.al_clips && w.al_cap >= w.cap_jobs) return;
+    free_align(w);
+    // rows of a cost matrix: the `not` row + at most n_max = n_text_ctx / 2 - 4 text tokens
+    const size_t rows = c->hp.n_text_ctx / 2 - 4 + 1, T = c->hp.n_audio_ctx, A = c->dtw_heads.size(), nj = w.cap_jobs;
+    dalloc(w.al_clips, nj * sizeof(AlignClip));
+    dalloc(w.al_stats, nj * A * T * 2 * sizeof(float));
+    dalloc(w.al_cost, nj * rows * T * sizeof(float));
+    dalloc(w.al_trace, nj * rows * T);
+    dalloc(w.al_fr, nj * rows * sizeof(int));
+    WM_CHECK(hipHostMalloc((void**)&w.h_al, nj * sizeof(AlignClip) + nj * rows * sizeof(int), 0));
+    w.al_cap = (int)nj;
+    w.al_rows = (int)rows;
+}
+
+// Align every window that just finished with new segments (Job::al_pending), all clips in one pass: the token
+// rows [sot, lang?, not, text.., eot] of each window run teacher-forced from position 0 through the unfused
+// prefill pass in the cached-K cross form, the alignment heads' softmaxed score rows are taken after each cross-Q
+// GEMM, then cost matrix, DTW and backtrace run on the device and the first frame of every text row comes back.
+// The pass overwrites the finished window's self-K/V rows of its slot: the clip's next window prefills from
+// position 0, so nothing reads them again. Runs before the clip's next encode replaces its encoder output and
+// cross K/V, and before the new-segment callback.
+static void align_windows(Sched& S) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const Vocab& v = c->vocab;
+    const Hparams& hp = c->hp;
+    struct Item { int job, n_sot, F; std::vector<int> toks; std::vector<TokenData*> text; };
+    std::vector<Item> items;
+    for (int k = 0; k < (int)S.jobs.size(); k++) {
+        Job& j = S.jobs[k];
+        if (!j.al_pending) continue;
+        j.al_pending = false;
+        Item it;
+        it.job = k;
+        it.F = std::min(j.al_frames / 2, hp.n_audio_ctx);
+        it.toks = {v.token_sot};
+        if (v.is_multilingual()) it.toks.push_back(v.token_sot + 1 + j.lang_id);
+        it.n_sot = (int)it.toks.size();
+        it.toks.push_back(v.token_not);
+        for (size_t g = j.al_seg0; g < j.result.size(); g++)
+            for (TokenData& td : j.result[g].tokens)
+                if (td.id < v.token_eot) { it.toks.push_back(td.id); it.text.push_back(&td); }
+        if (it.text.empty() || it.F < 1) continue;  // left unaligned
+        it.toks.push_back(v.token_eot);
+        items.push_back(std::move(it));
+    }
+    if (items.empty()) return;
+    const double t0 = now_ms();
+    ensure_align(c, s);
+    hipStream_t st = s->stream;
+    if (s->direct) {  // the clips' cross K/V from their encoder output, as prompts too long for the direct prefill
+        ensure_cross(c, s, w.cap_jobs);
+        std::vector<int> slots;
+        for (const Item& it : items) slots.push_back(S.jobs[it.job].slot);
+        ensure_cross_cache(c, s, slots);
+    }
+    const size_t A = c->dtw_heads.size(), T = hp.n_audio_ctx;
+    AlignClip* hc = (AlignClip*)w.h_al;
+    int* h_fr = (int*)(w.h_al + (size_t)w.al_cap * sizeof(AlignClip));
+    for (size_t i0 = 0; i0 < items.size();) {
+        // one group: as many clips as fit the token buffers and the score buffer
+        int nt = 0, ng = 0, max_rows = 0, max_n = 0, max_f = 0;
+        size_t p_el = 0, st_el = 0, i1 = i0;
+        int* hi = w.h_ints;
+        const int ct = w.cap_tok;
+        for (; i1 < items.size(); i1++) {
+            const Item& it = items[i1];
+            const int n = (int)it.toks.size();
+            const size_t pe = A * n * it.F;
+            if (ng > 0 && (nt + n > ct || (p_el + pe) * sizeof(float) > kAlignPBytes)) break;
+            if (n > ct) WM_FAIL("alignment: %d token rows do not fit the decoder workspace", n);
+            const Job& j = S.jobs[it.job];
+            AlignClip& cl = hc[ng++];
+            cl = AlignClip{};
+            cl.slot = j.slot; cl.row0 = nt; cl.n_rows = n; cl.n_sot = it.n_sot; cl.frames = it.F;
+            cl.p_off = (long)p_el; cl.st_off = (long)st_el;
+            cl.cost_off = (long)((size_t)j.slot * w.al_rows * T);
+            cl.tr_off = cl.cost_off;
+            cl.fr_off = (long)j.slot * w.al_rows;
+            p_el += pe;
+            st_el += A * it.F * 2;
+            for (int t = 0; t < n; t++) { hi[nt] = it.toks[t]; hi[ct + nt] = t; hi[2 * ct + nt] = j.slot; nt++; }
+            max_rows = std::max(max_rows, n);
+            max_n = std::max(max_n, n - it.n_sot - 1);
+            max_f = std::max(max_f, it.F);
+        }
+        if (p_el > w.al_P_elems) {
+            WM_CHECK(hipStreamSynchronize(st));
+            dfree(w.al_P);
+            w.al_P_elems = 0;
+            dalloc(w.al_P, p_el * sizeof(float));
+            w.al_P_elems = p_el;
+        }
+        WM_CHECK(hipMemcpyAsync(w.al_clips, hc, (size_t)ng * sizeof(AlignClip), hipMemcpyHostToDevice, st));
+        decoder_upload(c, s, nt, 0, true);
+        const AlignPass al{w.al_clips, ng, max_rows, nt, w.al_P};
+        const DecView dv{0, nt, st, w.splitk, w.splitk_elems, w.xo, w.xml};
+        s->step_rows = nt;
+        decoder_rows(c, s, dv, 0, false, false, 1.0, &al);
+        {
+            KT kt(s, K_ALIGN_COST, (double)p_el * 4 * 3);
+            launch_align_cost(w.al_P, w.al_clips, ng, (int)A, max_n, max_f, w.al_stats, w.al_cost, st);
+        }
+        {
+            KT kt(s, K_ALIGN_DTW, (double)ng * max_n * max_f * 5);
+            launch_align_dtw(w.al_cost, w.al_clips, ng, max_n, w.al_trace, w.al_fr, nullptr, nullptr, st);
+        }
+        WM_CHECK(hipMemcpyAsync(h_fr, w.al_fr, (size_t)w.al_cap * w.al_rows * sizeof(int), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        for (size_t i = i0; i < i1; i++) {
+            Item& it = items[i];
+            const Job& j = S.jobs[it.job];
+            const int* fr = h_fr + (size_t)j.slot * w.al_rows;
+            for (size_t r = 0; r < it.text.size(); r++) it.text[r]->t_dtw = j.al_seek + 2 * (int64_t)fr[r + 1];  // row 0 = `not`
+            s->align_info[it.job] = {(int)it.text.size() + 1, it.F, w.al_cost + (size_t)j.slot * w.al_rows * T};
+        }
+        i0 = i1;
+    }
+    S.t_align += now_ms() - t0;
 }
 
 // teacher-forcing hook (FullOpts::spot): the raw logits rows of the spot jobs among `act` (row r of
@@ -2040,7 +2297,9 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
         s->results.push_back(std::move(t->results[j]));
         s->lang_ids.push_back(t->lang_ids[j]);
         s->decisions.push_back(std::move(t->decisions[j]));
+        s->align_info.push_back(t->align_info[j]);  // (its cost matrix stays in the twin's workspace)
     }
+    s->align_ms = std::max(s->align_ms, t->align_ms);
     s->decoded_tokens += t->decoded_tokens;
     s->pdec_give_ups += t->pdec_give_ups;
     s->pdec_lost_ms += t->pdec_lost_ms;
@@ -2079,6 +2338,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     s->results.assign(n_jobs, {});
     s->lang_ids.assign(n_jobs, 0);
     s->decisions.assign(n_jobs, {});
+    s->align_info.assign(n_jobs, {});
+    s->align_ms = 0;
     s->decoded_tokens = 0;
     double t0 = now_ms();
     s->direct = pick_direct(c, n_jobs);
@@ -2281,6 +2542,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 }
             }
         }
+        // ---- token timestamps: align every window that just finished with new segments
+        if (c->dtw) align_windows(S);
         // ---- new-segment callback (whisper.h single-clip API)
         if (single_api && p.new_segment_callback) {
             Job& j = S.jobs[0];
@@ -2306,6 +2569,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     g_decoded_tokens_total += S.decoded;
     s->phase_ms[0] = S.t_mel; s->phase_ms[1] = S.t_enc; s->phase_ms[2] = S.t_prefill; s->phase_ms[3] = S.t_decode;
     s->phase_ms[4] = S.t_logits;
+    s->align_ms = S.t_align;
     std::lock_guard<std::mutex> lk(c->timings_mu);
     c->timings.encode_ms += (float)S.t_enc;
     c->timings.decode_ms += (float)S.t_decode;

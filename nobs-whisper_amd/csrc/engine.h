@@ -124,11 +124,20 @@ struct Context {
     // whisper_free orphans the ones a caller still holds, so a later whisper_free_state does not touch
     // the freed context (a garbage collector may finalise a context before its states)
     std::vector<whisper_state*> live;
+    // token timestamps from cross-attention DTW (whisper_context_params.dtw_token_timestamps): the alignment
+    // heads {layer, head} in list order, resolved once when the context is created (engine.cpp resolve_dtw)
+    bool dtw = false;
+    std::vector<std::pair<int, int>> dtw_heads;
+    std::mutex dtw_mu;
+    void* dtw_heads_dev = nullptr;  // int2 {head, index in dtw_heads} grouped by layer (dtw_layer_first)
+    std::vector<int> dtw_layer_first;  // [n_text_layer + 1]: layer l's entries of dtw_heads_dev
+    int dtw_last_layer = -1;
 };
 
 struct TokenData {
     int id, tid;
     float p, plog, pt, ptsum;
+    int64_t t_dtw = -1;  // 10 ms units; -1 = not aligned (DTW off, a timestamp token, an unaligned window)
 };
 
 struct Segment {
@@ -191,13 +200,24 @@ struct Workspace {
     int n_qtiles = 0;
     TokOut* h_tout = nullptr;
     SeqCtl* h_ctl = nullptr;
+    // token-timestamp alignment (contexts with dtw_token_timestamps only; allocated by the first aligned
+    // window): clip descriptors, score rows P of one group of clips (grown on demand), per-(head, frame)
+    // statistics, the cost matrix and DTW trace of every slot's last aligned window, first frames per row
+    AlignClip* al_clips = nullptr;
+    float *al_P = nullptr, *al_stats = nullptr, *al_cost = nullptr;
+    size_t al_P_elems = 0;
+    unsigned char* al_trace = nullptr;
+    int* al_fr = nullptr;
+    char* h_al = nullptr;  // pinned: [cap_jobs AlignClip][cap_jobs * al_rows int]
+    int al_cap = 0, al_rows = 0;
 };
 
 struct Job;
 
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
-enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER, K_NCLASS };
+enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 }  // namespace wm
@@ -223,6 +243,11 @@ struct whisper_state {
     int n_len = 0, n_len_org = 0;  // last mel
     std::vector<float> logits_host;
     double phase_ms[5] = {0, 0, 0, 0, 0};
+    double align_ms = 0;  // token-timestamp alignment passes of the last call
+    // per job of the last call: the cost matrix of its last aligned window (rows x frames f32 on the device,
+    // in this state's or its twin's workspace); rows = 0: no window of the job was aligned
+    struct AlignInfo { int rows = 0, frames = 0; const float* cost = nullptr; };
+    std::vector<AlignInfo> align_info;
     long decoded_tokens = 0;
     // standalone encode/decode API support
     int last_enc_windows = 0;
@@ -274,6 +299,9 @@ void recover_state(whisper_state* s);
 // frees the states kept in the context's pool (whisper_free)
 void drain_state_pool(Context* c);
 void orphan_states(Context* c);
+// alignment heads of a context from its whisper_context_params; false (one stderr line) when the
+// configuration is invalid for the model
+bool resolve_dtw(Context* c, const whisper_context_params& cp);
 
 struct FullOpts {
     int fixed_tokens = 0;

@@ -178,6 +178,32 @@ void launch_xattn_step(DType dt, const void* enc, const int* slot, const void* q
 void launch_xattn_combine(DType dt, const float* opart, const float* ml, int splits, const void* wv, const float* bv, int n,
                           int d, int H, void* out, hipStream_t st);
 
+// ---- token timestamps from cross-attention DTW (kernels/align.hip) -------------------------------
+// One clip of an alignment launch. Its token rows are rows [row0, row0 + n_rows) of the pass's q, over
+// cross-cache slot `slot`; n_sot = 1 or 2 leading rows and the last row (eot) are not aligned, so the cost
+// matrix has N = n_rows - n_sot - 1 rows; `frames` = F <= n_audio_ctx encoder positions. Offsets in
+// elements of their buffers: P [A][n_rows][F] f32, stats [A][F][2] f32, cost [N][F] f32, trace [N][F]
+// bytes, fr [N] int, path [N + F] int pairs.
+struct AlignClip {
+    int slot, row0, n_rows, n_sot, frames, pad;
+    long p_off, st_off, cost_off, tr_off, fr_off, path_off;
+};
+// Softmaxed score rows of the alignment heads of one decoder layer: heads[k] = {head, index a in the
+// context's head list} (device, n_heads entries); q [rows][q_stride] in the compute type (cross-Q of that
+// layer, already scaled), cross = the cross K/V cache [slot][L][2][H][ctx][64]. P[a][i][t] =
+// softmax_t(q_i . k_t) over all ctx keys in f32, written for t < F only. K is read once per (clip, head).
+void launch_align_scores(DType dt, const void* q, int q_stride, const void* cross, const AlignClip* clips, int n_clips,
+                         int max_rows, int L, int layer, int H, int ctx, const int2* heads, int n_heads, float* P,
+                         hipStream_t st);
+// z-score per (head, frame) over the token rows, width-7 median along the frames, head mean, negation,
+// row slice: P -> cost (stats is scratch). max_rows / max_frames: the largest N / F of the clips.
+void launch_align_cost(const float* P, const AlignClip* clips, int n_clips, int A, int max_rows, int max_frames, float* stats,
+                       float* cost, hipStream_t st);
+// OpenAI's dtw_cpu in f32, one workgroup per clip: fr[r] = frame of the first path point of cost row r.
+// trace is scratch; path / path_len (optional) receive the path from (N - 1, F - 1) back to (0, 0).
+void launch_align_dtw(const float* cost, const AlignClip* clips, int n_clips, int max_n, unsigned char* trace, int* fr,
+                      int* path, int* path_len, hipStream_t st);
+
 // ---- persistent decode step (kernels/pdec.hip) ---------------------------------------------------
 // One launch = every decoder layer of one decode step for M <= kPdecMaxRows clips in the cross K/V cache
 // form, phases handed off through data-tagged granules (see pdec.hip). Output: out_dh [M][d] (T) = the final

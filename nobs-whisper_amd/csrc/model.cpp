@@ -506,6 +506,7 @@ void free_context(Context* c) {
     if (c && c->arena_exp) { hipSetDevice(c->device); hipFree(c->arena_exp); c->arena_exp = nullptr; }
     if (c && c->pdec_layers) { hipSetDevice(c->device); hipFree(c->pdec_layers); c->pdec_layers = nullptr; }
     if (c && c->pdec_layers_exp) { hipSetDevice(c->device); hipFree(c->pdec_layers_exp); c->pdec_layers_exp = nullptr; }
+    if (c && c->dtw_heads_dev) { hipSetDevice(c->device); hipFree(c->dtw_heads_dev); c->dtw_heads_dev = nullptr; }
 }
 
 }  // namespace wm

@@ -30,8 +30,18 @@ FP8_ENC = 2  # bf16 with the encoder QKV/FC1/FC2 GEMMs in fp8 e4m3 (large-v3-tur
 GREEDY, BEAM_SEARCH = 0, 1
 
 
+class WhisperAhead(C.Structure):
+    _fields_ = [("n_text_layer", C.c_int), ("n_head", C.c_int)]
+
+
 class WhisperAheads(C.Structure):
     _fields_ = [("n_heads", C.c_size_t), ("heads", C.c_void_p)]
+
+
+# enum whisper_alignment_heads_preset (include/whisper.h); whisper-rs: DtwModelPreset / DtwMode
+AHEADS = {name: i for i, name in enumerate(
+    ["NONE", "N_TOP_MOST", "CUSTOM", "TINY_EN", "TINY", "BASE_EN", "BASE", "SMALL_EN", "SMALL", "MEDIUM_EN", "MEDIUM",
+     "LARGE_V1", "LARGE_V2", "LARGE_V3", "LARGE_V3_TURBO"])}
 
 
 class WhisperContextParams(C.Structure):
@@ -157,6 +167,11 @@ def lib() -> C.CDLL:
         "whisper_mi355x_batch_decoded_tokens": (C.c_long, [vp]),
         "whisper_mi355x_window_decisions": (C.c_int, [vp, C.c_int, C.POINTER(WindowDecision), C.c_int]),
         "whisper_mi355x_phase_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "whisper_mi355x_align_ms": (C.c_double, [vp]),
+        "whisper_mi355x_align_cost": (C.c_int, [vp, C.c_int, fp, C.c_long, ip, ip]),
+        "whisper_mi355x_debug_align_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, ip, ip, C.c_int, ip, ip, vp]),
+        "whisper_mi355x_debug_align_cost": (C.c_int, [vp, vp, C.c_int, ip, ip, ip, C.c_int, vp]),
+        "whisper_mi355x_debug_align_dtw": (C.c_int, [vp, vp, C.c_int, ip, ip, ip, ip, ip]),
         "whisper_mi355x_get_mel": (C.c_int, [vp, fp, C.c_int]),
         "whisper_mi355x_get_encoder_out": (C.c_int, [vp, fp, C.c_int]),
         "whisper_mi355x_state_stream": (vp, [vp]),
@@ -222,11 +237,26 @@ def reference_full_params(language: str | None = "en", initial_prompt: str | Non
 
 
 class WhisperContext:
-    def __init__(self, path: str, dtype: int = F16, gpu_device: int = 0, load_weights: bool = True):
+    def __init__(self, path: str, dtype: int = F16, gpu_device: int = 0, load_weights: bool = True,
+                 dtw_preset=None, dtw_n_top: int = -1, dtw_heads=None):
+        """dtw_preset (an AHEADS name or value), dtw_n_top (every head of the top n text layers) or dtw_heads
+        ([(layer, head), ...]) turn token-level DTW timestamps on (whisper-rs DtwParameters); all three at their
+        defaults: off."""
         L = lib()
         cp = L.whisper_context_default_params()
         cp.use_gpu = True
         cp.gpu_device = gpu_device
+        if dtw_preset is not None or dtw_n_top != -1 or dtw_heads is not None:
+            cp.dtw_token_timestamps = True
+            if dtw_preset is not None:
+                cp.dtw_aheads_preset = AHEADS[dtw_preset] if isinstance(dtw_preset, str) else int(dtw_preset)
+            else:
+                cp.dtw_aheads_preset = AHEADS["CUSTOM"] if dtw_heads is not None else AHEADS["N_TOP_MOST"]
+            cp.dtw_n_top = dtw_n_top
+            if dtw_heads is not None:
+                heads = (WhisperAhead * max(1, len(dtw_heads)))(*[WhisperAhead(l, h) for l, h in dtw_heads])
+                cp.dtw_aheads.n_heads = len(dtw_heads)
+                cp.dtw_aheads.heads = C.cast(heads, C.c_void_p)  # (copied by the init; `heads` lives until then)
         self.L = L
         self.gpu_device = gpu_device
         self._states = weakref.WeakSet()
@@ -387,6 +417,37 @@ class WhisperState:
         out = (C.c_double * 5)()
         self.L.whisper_mi355x_phase_ms(self.ptr, out)
         return dict(zip(["mel", "encode", "prefill", "decode", "logits"], list(out)))
+
+    def align_ms(self) -> float:
+        """Wall time of the token-timestamp alignment passes of the last full / full_batch call."""
+        return float(self.L.whisper_mi355x_align_ms(self.ptr))
+
+    def token_times(self, job: int = 0) -> list:
+        """Per segment of the job, per token: (id, t_dtw); t_dtw in 10 ms units, -1 = not aligned."""
+        L = self.L
+        out = []
+        for i in range(L.whisper_mi355x_batch_n_segments(self.ptr, job)):
+            row = []
+            for t in range(L.whisper_mi355x_batch_segment_n_tokens(self.ptr, job, i)):
+                d = L.whisper_mi355x_batch_token_data(self.ptr, job, i, t)
+                row.append((d.id, d.t_dtw))
+            out.append(row)
+        return out
+
+    def align_cost(self, job: int = 0):
+        """The DTW cost matrix [rows][frames] (float32) of the job's last aligned window, or None."""
+        import numpy as np
+        rows, frames = C.c_int(0), C.c_int(0)
+        rc = self.L.whisper_mi355x_align_cost(self.ptr, job, None, 0, C.byref(rows), C.byref(frames))
+        if rc == -1:
+            raise IndexError(job)
+        if rows.value <= 0:
+            return None
+        out = np.empty((rows.value, frames.value), np.float32)
+        rc = self.L.whisper_mi355x_align_cost(self.ptr, job, out.ctypes.data_as(C.POINTER(C.c_float)), out.size,
+                                              C.byref(rows), C.byref(frames))
+        assert rc == 0, rc
+        return out
 
     def close(self):
         if self.ptr:
