@@ -212,6 +212,31 @@ WHISPER_API int whisper_mi355x_debug_xattn(struct whisper_context * ctx, const v
                                            int n, int n_ctx, int d, float scale, int splits, float rescale_thr,
                                            void * out, int reps, float * ms);
 
+/* Debug: the decoder attention launchers (kernels/attn.hip) on caller data, one launch each, every pointer a
+ * device pointer, the caches and out in the context's compute type; d = 64 H. cache
+ * [slots][L][2][H][n_ctx][64] (K | V per layer), slot [n] (int).
+ * self_step: slabs [splits][n][3d] (f32 split-K partial sums of q | k | v), bias [3d] (f32, may be null);
+ *   q = T((sum + bias) scale), k likewise, v = T(sum + bias); k, v are written to cache rows pos[i] and token i
+ *   attends rows [0, pos[i]] -> out [n][d]. n_ctx <= 448.
+ * cross_step: slabs [splits][n][d] (q only), bias [d]; token i attends rows [0, n_kv[i]) -> out [n][d]; the
+ *   launcher picks the 1024- or the 256-thread kernel from n (WHISPER_MI355X_XWIDE_MAX). n_ctx <= 1536.
+ * prefill: q [tokens][q_stride] (already scaled), tiles [n_tiles] int pairs {first token, count <= 64} (runs of
+ *   consecutive tokens of one slot, n_kv non-decreasing), slot / n_kv per token -> out [tokens][d].
+ * Return 0, -1 on bad arguments (null ctx, n <= 0, splits outside 1..16), or the runtime error code when the
+ * launcher refuses the shape (nothing is launched). */
+WHISPER_API int whisper_mi355x_debug_attn_self_step(struct whisper_context * ctx, const float * slabs, int splits,
+                                                    const float * bias, float scale, void * cache, const int * slot,
+                                                    const int * pos, int n, int L, int layer, int H, int n_ctx,
+                                                    void * out);
+WHISPER_API int whisper_mi355x_debug_attn_cross_step(struct whisper_context * ctx, const float * slabs, int splits,
+                                                     const float * bias, float scale, const void * cache,
+                                                     const int * slot, const int * n_kv, int n, int L, int layer,
+                                                     int H, int n_ctx, void * out);
+WHISPER_API int whisper_mi355x_debug_attn_prefill(struct whisper_context * ctx, const void * q, int q_stride,
+                                                  const void * cache, const int * slot, const int * n_kv,
+                                                  const void * tiles, int n_tiles, int L, int layer, int H, int n_ctx,
+                                                  void * out);
+
 /* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
  * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.
  * scores: q [n_text_layer][sum n_rows][d] (device, compute type: the cross-Q rows of every layer, already scaled

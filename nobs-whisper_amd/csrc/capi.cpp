@@ -847,6 +847,62 @@ int whisper_mi355x_debug_xattn(struct whisper_context* ctx, const void* enc, con
     });
 }
 
+// ---- decoder attention (kernels/attn.hip) on caller data: one launch each, all device pointers ----------
+// the hook's stream, destroyed also when the launcher refuses the shape (WM_FAIL throws)
+struct HookStream {
+    hipStream_t st = nullptr;
+    HookStream() { WM_CHECK(hipStreamCreate(&st)); }
+    ~HookStream() { hipStreamDestroy(st); }
+};
+// slabs [splits][n][3d] f32 (q | k | v partial sums), bias [3d] f32 or null, cache
+// [slots][L][2][H][n_ctx][64] in the context dtype (K[pos], V[pos] are written), slot / pos [n] int -> out [n][d]
+int whisper_mi355x_debug_attn_self_step(struct whisper_context* ctx, const float* slabs, int splits, const float* bias,
+                                        float scale, void* cache, const int* slot, const int* pos, int n, int L,
+                                        int layer, int H, int n_ctx, void* out) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || n <= 0 || splits < 1 || splits > 16) return -1;
+        hipSetDevice(ctx->c.device);
+        const int d = 64 * H;
+        const DecSlabs sl{slabs, splits, (long)n * 3 * d, 3 * d, bias, scale};
+        HookStream hs;
+        hipStream_t st = hs.st;
+        launch_attn_self_step(ctx->c.dt, sl, cache, slot, pos, n, L, layer, H, n_ctx, d, out, st);
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+// slabs [splits][n][d] f32 (cross-Q partial sums), bias [d] f32 or null, n_kv [n] int (keys per token); the
+// launcher picks the 1024- or the 256-thread kernel by n
+int whisper_mi355x_debug_attn_cross_step(struct whisper_context* ctx, const float* slabs, int splits, const float* bias,
+                                         float scale, const void* cache, const int* slot, const int* n_kv, int n, int L,
+                                         int layer, int H, int n_ctx, void* out) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || n <= 0 || splits < 1 || splits > 16) return -1;
+        hipSetDevice(ctx->c.device);
+        const int d = 64 * H;
+        const DecSlabs sl{slabs, splits, (long)n * d, d, bias, scale};
+        HookStream hs;
+        hipStream_t st = hs.st;
+        launch_attn_cross_step(ctx->c.dt, sl, cache, slot, n_kv, n, L, layer, H, n_ctx, d, out, st);
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+// q [tokens][q_stride] (already scaled), tiles [n_tiles] int pairs {first token, count <= 64}, slot / n_kv per token
+int whisper_mi355x_debug_attn_prefill(struct whisper_context* ctx, const void* q, int q_stride, const void* cache,
+                                      const int* slot, const int* n_kv, const void* tiles, int n_tiles, int L,
+                                      int layer, int H, int n_ctx, void* out) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || n_tiles <= 0) return -1;
+        hipSetDevice(ctx->c.device);
+        HookStream hs;
+        hipStream_t st = hs.st;
+        launch_attn_prefill(ctx->c.dt, q, q_stride, cache, slot, n_kv, tiles, n_tiles, L, layer, H, n_ctx, 64 * H, out, st);
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+
 // ---- token-timestamp alignment kernels (kernels/align.hip) on caller data ------------------------------
 // clip descriptors with the packed offsets the three hooks share: P [A][n_rows][F], cost [N][F], fr [N],
 // path [N + F] pairs, clip after clip

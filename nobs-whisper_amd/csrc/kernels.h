@@ -134,13 +134,10 @@ void launch_gemm_small(DType dt, int epi, const GemmArgs& a, bool lna, hipStream
 // 1 / 2 / 3 / 5 (attn_enc_kernel / _enc2_ / _enc3_ / _enc2_ with packed FMAs; kernel benchmarks only)
 void launch_attn_encoder(DType dt, const void* qkv, void* out, int B, int T, int d, int H, hipStream_t st,
                          int variant = -1);
-// single-query attention for decoder tokens over a cache [slot][L][2][H][ctx][64]:
-// token i attends keys [0, n_kv[i]) of slot[i]; q [n][q_stride] at head h offset h*64; out [n][d]
-void launch_attn_decode(DType dt, const void* q, int q_stride, const void* cache, const int* slot, const int* n_kv,
-                        int n, int L, int layer, int H, int ctx, int d, void* out, int kind, hipStream_t st);
-
-// Prefill: the same attention for runs of consecutive tokens of one clip, tiles[t] = {first token,
-// count <= 64} (int2), one workgroup per (tile, head); K/V staged once per tile.
+// Decoder attention over a cache [slot][L][2][H][ctx][64]: token i attends keys [0, n_kv[i]) of slot[i];
+// q [n][q_stride] at head h offset h*64; out [n][d].
+// Prefill: runs of consecutive tokens of one clip, tiles[t] = {first token, count <= 64} (int2), one
+// workgroup per (tile, head); K/V staged once per tile.
 void launch_attn_prefill(DType dt, const void* q, int q_stride, const void* cache, const int* slot, const int* n_kv,
                          const void* tiles, int n_tiles, int L, int layer, int H, int ctx, int d, void* out,
                          hipStream_t st);
@@ -156,7 +153,7 @@ struct DecSlabs {
 void launch_attn_self_step(DType dt, const DecSlabs& sl, void* cache, const int* slot, const int* pos, int n, int L,
                            int layer, int H, int ctx, int d, void* out, hipStream_t st);
 // decode steps of up to this many clips use the 1024-thread cache-form kernel (WHISPER_MI355X_XWIDE_MAX,
-// default 4, read per call)
+// default 8, read per call)
 int attn_cross_wide_max();
 // cross attention of token i over n_kv[i] keys of the cross cache; q from the cross-Q slabs.
 void launch_attn_cross_step(DType dt, const DecSlabs& sl, const void* cache, const int* slot, const int* n_kv, int n,

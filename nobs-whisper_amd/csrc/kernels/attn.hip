@@ -691,22 +691,8 @@ __device__ __forceinline__ void attn_dec_body(const T* __restrict__ q, int q_str
     }
 }
 
-// One body, three kernel names so profiles separate the uses: the self cache (prefill), the cross
-// cache in a decode step (one token per clip, q reduced from slabs: the roofline kernel) and the
-// cross cache in a prefill.
-template <typename T>
-__global__ void __launch_bounds__(256) attn_self_kernel(const T* __restrict__ q, int q_stride, const T* __restrict__ cache,
-                                                        const int* __restrict__ slot, const int* __restrict__ n_kv_arr,
-                                                        int L, int layer, int H, int ctx, int d, T* __restrict__ out) {
-    attn_dec_body<T, false>(q, q_stride, DecSlabs{}, cache, slot, n_kv_arr, L, layer, H, ctx, d, out);
-}
-template <typename T>
-__global__ void __launch_bounds__(256) attn_cross_prefill_kernel(const T* __restrict__ q, int q_stride,
-                                                                 const T* __restrict__ cache, const int* __restrict__ slot,
-                                                                 const int* __restrict__ n_kv_arr, int L, int layer, int H,
-                                                                 int ctx, int d, T* __restrict__ out) {
-    attn_dec_body<T, false>(q, q_stride, DecSlabs{}, cache, slot, n_kv_arr, L, layer, H, ctx, d, out);
-}
+// One body, two kernel names so profiles separate the widths: the cross cache in a decode step (one
+// token per clip, q reduced from slabs: the roofline kernel) at 256 and at 1024 threads.
 template <typename T>
 __global__ void __launch_bounds__(256) attn_cross_step_kernel(const DecSlabs sl, const T* __restrict__ cache,
                                                               const int* __restrict__ slot, const int* __restrict__ n_kv_arr,
@@ -1084,23 +1070,6 @@ void launch_attn_encoder(DType dt, const void* qkv, void* out, int B, int Tn, in
     dim3 grid(cdiv(Tn, 64), H, B);
     if (dt == DType::F16) attn_enc_kernel<half_t><<<grid, 256, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
     else attn_enc_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
-}
-
-void launch_attn_decode(DType dt, const void* q, int q_stride, const void* cache, const int* slot, const int* n_kv, int n,
-                        int L, int layer, int H, int ctx, int d, void* out, int kind, hipStream_t st) {
-    if (n <= 0) return;
-    if (ctx > 1536) WM_FAIL("attention context %d > 1536", ctx);
-    dim3 grid(n, H);
-#define WM_ATTN_DEC(TT, KN) \
-    KN<TT><<<grid, 256, 0, st>>>((const TT*)q, q_stride, (const TT*)cache, slot, n_kv, L, layer, H, ctx, d, (TT*)out)
-    if (dt == DType::F16) {
-        if (kind == 2) WM_ATTN_DEC(half_t, attn_cross_prefill_kernel);
-        else WM_ATTN_DEC(half_t, attn_self_kernel);
-    } else {
-        if (kind == 2) WM_ATTN_DEC(bf16_t, attn_cross_prefill_kernel);
-        else WM_ATTN_DEC(bf16_t, attn_self_kernel);
-    }
-#undef WM_ATTN_DEC
 }
 
 // WHISPER_MI355X_XWIDE_MAX (default 8, read per call): decode steps of up to this many clips use the
