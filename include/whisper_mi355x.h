@@ -145,7 +145,8 @@ WHISPER_API long whisper_mi355x_pdec_give_ups(struct whisper_state * state);
 /* Kernel-level test/tuning hooks (device pointers): one fused-epilogue GEMM launch of the engine
  * (epi as in kernels.h: 0 store, 1 gelu, 2 residual f32, 4 f32, 5 cross K/V: out is then a cross cache of
  * M / n_audio_ctx slots for N / 2K layers, K = d), averaged over reps; and the
- * GEMM variant override (-1 auto, 0 register-staged, 1 LDS-DMA). */
+ * GEMM variant override: -1 auto; 0 register-staged kernels only; 1 LDS-DMA, 128x128 tiles in place of the
+ * 256x256 phase-interleaved kernel; >= 2 the 256x256 phase-interleaved kernel wherever the shape is big. */
 WHISPER_API int whisper_mi355x_debug_gemm(struct whisper_context * ctx, int epi, const void * A, int M, int K,
                                           const void * B, int N, const float * bias, void * out, int reps, float * ms);
 WHISPER_API void whisper_mi355x_set_gemm_variant(int variant);
@@ -175,8 +176,6 @@ WHISPER_API void whisper_mi355x_set_pdec_stamps(void * dev);
 /* Quantized files: 1 = persistent decode steps stream the GGML blocks; 0 (default) = they read the
  * context's expanded compute-type copy once it exists (faster). */
 WHISPER_API void whisper_mi355x_set_pdec_blocks(int on);
-/* Debug/tuning: the decode-step residual GEMM with its fused LayerNorm (M <= 128):
- * x[M][N] (f32, in/out) += A.B^T + bias, then y[M][N] (compute dtype) = LN(x) * ln_w + ln_b. */
 // fp8 (OCP e4m3) GEMM with per-row f32 scales (A per row m, B per row n), then epilogue `epi`;
 // A8 [M][K], B8 [N][K] bytes, K % 128 == 0 (large-v3-turbo fp8 encoder path)
 WHISPER_API int whisper_mi355x_debug_gemm_fp8(struct whisper_context * ctx, int epi, const void * A8,
@@ -193,10 +192,14 @@ WHISPER_API int whisper_mi355x_debug_gemm_w8(struct whisper_context * ctx, int e
 WHISPER_API int whisper_mi355x_debug_quant_fp8(struct whisper_context * ctx, const void * x, long rows, int K,
                                                void * q, float * s);
 /* Debug/tuning: one encoder self-attention launch (device pointers): qkv [B*T][3d] (Q | K | V, compute
- * type of ctx), out [B*T][d]; variant 1 / 2 / 3 / 5 = attn_enc_kernel / attn_enc2_kernel / attn_enc3_kernel /
- * attn_enc2_kernel held to 128 VGPRs, two workgroups per CU (d = 64 H). The first launch's result stays in out; reps more launches are timed (ms per launch). */
+ * type of ctx), out [B*T][d], d = 64 H; variant 6 = the production launch (attn_enc2_kernel held to 128 VGPRs,
+ * two workgroups per CU, scalar softmax FMAs, XCD-grouped grid), 2 = the plain attn_enc2_kernel (the tests'
+ * bitwise reference); any other variant returns -1. The first launch's result stays in out; reps more launches
+ * are timed (ms per launch). */
 WHISPER_API int whisper_mi355x_debug_attn_encoder(struct whisper_context * ctx, const void * qkv, int B, int T, int d,
                                                   int H, int variant, void * out, int reps, float * ms);
+/* Debug/tuning: the decode-step residual GEMM with its fused LayerNorm (M <= 128):
+ * x[M][N] (f32, in/out) += A.B^T + bias, then y[M][N] (compute dtype) = LN(x) * ln_w + ln_b. */
 WHISPER_API int whisper_mi355x_debug_gemm_ln(struct whisper_context * ctx, const void * A, int M, int K,
                                              const void * B, int N, const float * bias, float * x,
                                              const float * ln_w, const float * ln_b, void * y, int reps, float * ms);

@@ -609,6 +609,9 @@ int whisper_mi355x_debug_gemm(struct whisper_context* ctx, int epi, const void* 
                               const float* bias, void* out, int reps, float* ms) {
     return guarded(nullptr, [&]() -> int {
         if (!ctx) return -1;
+        // out of EPI_CROSSKV = a cross cache [M / n_audio_ctx][N / 2K][2][K / 64][n_audio_ctx][64], slots in order
+        const int T = ctx->c.hp.n_audio_ctx;
+        if (epi == EPI_CROSSKV && (M % T != 0 || K % 64 != 0 || N % (2 * K) != 0)) return -1;
         hipSetDevice(ctx->c.device);
         hipStream_t st;
         WM_CHECK(hipStreamCreate(&st));
@@ -622,9 +625,7 @@ int whisper_mi355x_debug_gemm(struct whisper_context* ctx, int epi, const void* 
             WM_CHECK(hipMalloc(&g.splitk_ws, g.splitk_ws_elems * sizeof(float)));
         }
         int* dslot = nullptr;
-        if (epi == EPI_CROSSKV) {  // out = a cross cache [M / n_audio_ctx][N / 2K][2][K / 64][n_audio_ctx][64], slots in order
-            const int T = ctx->c.hp.n_audio_ctx;
-            if (M % T != 0 || K % 64 != 0 || N % (2 * K) != 0) return -1;
+        if (epi == EPI_CROSSKV) {
             std::vector<int> hs(M / T);
             for (int i = 0; i < M / T; i++) hs[i] = i;
             WM_CHECK(hipMalloc((void**)&dslot, hs.size() * sizeof(int)));
@@ -747,7 +748,7 @@ int whisper_mi355x_debug_quant_fp8(struct whisper_context* ctx, const void* x, l
 int whisper_mi355x_debug_attn_encoder(struct whisper_context* ctx, const void* qkv, int B, int T, int d, int H,
                                       int variant, void* out, int reps, float* ms) {
     return guarded(nullptr, [&]() -> int {
-        if (!ctx || B < 1 || T < 1 || d != 64 * H || variant < 1 || variant > 6 || variant == 4) return -1;
+        if (!ctx || B < 1 || T < 1 || d != 64 * H || (variant != 2 && variant != 6)) return -1;
         hipSetDevice(ctx->c.device);
         hipStream_t st;
         WM_CHECK(hipStreamCreate(&st));

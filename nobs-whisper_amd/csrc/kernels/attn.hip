@@ -1,11 +1,12 @@
 // Attention kernels.
 //
-// Encoder: flash-style self-attention over the 1500 audio positions, d_head = 64, one workgroup =
-// 64 queries of one (chunk, head), 4 waves x 16 query rows. K tiles are staged in LDS row-major
-// (XOR-swizzled 16-byte chunks) and V tiles transposed, so S = Q.K^T and O += P.V are both
-// v_mfma_f32_16x16x32 with ds_read_b128 operand fetches. Softmax runs online per row (16 lanes
-// per row, xor-shuffle reductions), P is rounded to the MFMA input type before P.V as ggml does.
-// Roofline: MFMA-bound (4*T^2*64 FLOP per head).
+// Encoder (attn_enc2_kernel): flash-style self-attention over the 1500 audio positions, d_head = 64,
+// in the swapped-product form S^T = K.Q^T, O^T += V^T.P^T (v_mfma_f32_32x32x16). One workgroup = 256
+// queries of one (window, head), 8 waves x 32 queries; K and V tiles of 64 keys are double-buffered in
+// LDS row-major (XOR-swizzled 16-byte chunks), V^T comes from transposing LDS reads, and P never
+// leaves registers: the score accumulator, rounded to the MFMA input type as ggml rounds P, is the
+// second product's B operand. Softmax runs online per query in base 2. Roofline: MFMA-bound
+// (4*T^2*64 FLOP per head).
 //
 // Decoder: one query per (token, head) over a KV cache [slot][L][2][H][ctx][64] — the self cache
 // (ctx 448, n_kv = pos+1) or the cross cache (ctx 1500). Three phases in one workgroup: scores
@@ -20,137 +21,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int swz(int row, int ch) { return ch ^ ((row >> 1) & 7); }
 
-template <typename T>
-__global__ void __launch_bounds__(256) attn_enc_kernel(const T* __restrict__ qkv, T* __restrict__ out, int Tn, int d) {
-    typedef typename Frag<T>::type FT;
-    const int qb = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const long base = (long)b * Tn;
-    const int ld = 3 * d;
-    __shared__ u32x4 Ks[64 * 8];
-    __shared__ u32x4 Vts[64 * 8];
-    __shared__ u32x4 Ps[4][16 * 8];
-
-    const u32x4 zero = {0, 0, 0, 0};
-    FT qf[2];
-    {
-        const int qrow = qb * 64 + wave * 16 + (lane & 15);
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const int ch = s * 4 + (lane >> 4);
-            u32x4 v = qrow < Tn ? *(const u32x4*)(qkv + (base + qrow) * ld + h * 64 + ch * 8) : zero;
-            qf[s] = __builtin_bit_cast(FT, v);
-        }
-    }
-    float m_i[4], l_i[4];
-    f32x4 o[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) { m_i[r] = -INFINITY; l_i[r] = 0.0f; o[r] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-
-    const int n_kt = (Tn + 63) / 64;
-    T* Vt_el = (T*)Vts;
-    T* P_el = (T*)Ps[wave];
-    for (int kt = 0; kt < n_kt; kt++) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int c = tid + i * 256, key = c >> 3, kc = c & 7;
-            const int kg = kt * 64 + key;
-            u32x4 kv = zero, vv = zero;
-            if (kg < Tn) {
-                kv = *(const u32x4*)(qkv + (base + kg) * ld + d + h * 64 + kc * 8);
-                vv = *(const u32x4*)(qkv + (base + kg) * ld + 2 * d + h * 64 + kc * 8);
-            }
-            Ks[key * 8 + swz(key, kc)] = kv;
-            const T* ve = (const T*)&vv;
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int dim = kc * 8 + e;
-                Vt_el[(dim * 8 + swz(dim, key >> 3)) * 8 + (key & 7)] = ve[e];
-            }
-        }
-        __syncthreads();
-        f32x4 sacc[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            sacc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const int row = j * 16 + (lane & 15);
-                const FT kf = __builtin_bit_cast(FT, Ks[row * 8 + swz(row, s * 4 + (lane >> 4))]);
-                sacc[j] = mfma16x16x32(qf[s], kf, sacc[j]);
-            }
-        }
-        float mx[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) mx[r] = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int key = kt * 64 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const float v = key < Tn ? sacc[j][r] * 0.125f : -INFINITY;
-                sacc[j][r] = v;
-                mx[r] = fmaxf(mx[r], v);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-#pragma unroll
-            for (int o2 = 1; o2 < 16; o2 <<= 1) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], o2));
-        }
-        float alpha[4], rs[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float mn = fmaxf(m_i[r], mx[r]);
-            alpha[r] = __expf(m_i[r] - mn);
-            m_i[r] = mn;
-            rs[r] = 0.0f;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const T pt = (T)__expf(sacc[j][r] - m_i[r]);
-                rs[r] += (float)pt;
-                const int row = (lane >> 4) * 4 + r, key = j * 16 + (lane & 15);
-                P_el[(row * 8 + swz(row, key >> 3)) * 8 + (key & 7)] = pt;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-#pragma unroll
-            for (int o2 = 1; o2 < 16; o2 <<= 1) rs[r] += __shfl_xor(rs[r], o2);
-            l_i[r] = l_i[r] * alpha[r] + rs[r];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) o[j][r] *= alpha[r];
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's P stores landed
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const int prow = lane & 15;
-            const FT pf = __builtin_bit_cast(FT, Ps[wave][prow * 8 + swz(prow, s * 4 + (lane >> 4))]);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int vrow = j * 16 + (lane & 15);
-                const FT vf = __builtin_bit_cast(FT, Vts[vrow * 8 + swz(vrow, s * 4 + (lane >> 4))]);
-                o[j] = mfma16x16x32(pf, vf, o[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int row = qb * 64 + wave * 16 + (lane >> 4) * 4 + r;
-        if (row >= Tn) continue;
-        const float inv = 1.0f / l_i[r];
-#pragma unroll
-        for (int j = 0; j < 4; j++) out[(base + row) * d + h * 64 + j * 16 + (lane & 15)] = (T)(o[j][r] * inv);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Encoder self-attention, swapped-product form. One workgroup = 256 queries of one (window, head):
 // 8 waves x 32 queries; K/V tiles of 64 keys double-buffered in LDS (one barrier per tile, the next
@@ -163,14 +33,15 @@ __global__ void __launch_bounds__(256) attn_enc_kernel(const T* __restrict__ qkv
 //                             the permuted key order of that layout), A = V^T via
 //                             ds_read_b64_tr_b16 from a row-major V image (no transposing store)
 // Exponentials in base 2 with the 1/8 scale and log2(e) folded into one FMA.
-// MINW = 4 (variant 5; with PK = false variant 6, the default): the register allocation held to 128 VGPRs so that two workgroups
+// MINW = 4 (with PK = false: variant 6, the default): the register allocation held to 128 VGPRs so that two workgroups
 // share a CU (4 waves per SIMD); they drift apart between their barriers, so one workgroup's softmax
 // runs beside the other's MFMAs: 578 vs 694 us per 32-window large-v3 launch (random bf16 operands,
 // profiles/r03_attn_encoder_variants.txt). MINW = 1 (variant 2): 138 VGPRs, one workgroup per CU.
 // PK = false (variant 6): the exponent arguments and row sums as scalar v_fma_f32 / v_add_f32 (inline asm,
 // so the compiler cannot re-pack them) instead of v_pk_fma_f32 / v_pk_add_f32, which the guide prices
 // above two scalar ops beside MFMAs; the same per-element operations, so the same bits. No VGPR spill at
-// 128 (variant 5: 2); encode 325.9 -> 324.6 ms per step at 128 clips (profiles/r03_attn_encoder_variants.txt).
+// 128 (the packed form at MINW = 4 spilled 2); encode 325.9 -> 324.6 ms per step at 128 clips
+// (profiles/r03_attn_encoder_variants.txt).
 // XCD (round 6): a 1-D grid of nqb x H x B workgroups whose id L runs on XCD L % 8; workgroup L takes the
 // (query block, head, window) of index (L % 8) * (G / 8) + L / 8, so the query blocks of one (window, head)
 // share an XCD and its L2 fetches their K / V once (id order: they were consecutive ids, i.e. up to 6
@@ -345,170 +216,6 @@ __global__ void __launch_bounds__(512, MINW) attn_enc2_kernel(const T* __restric
             Vs[cur ^ 1][v_slot] = nv;
         }
         __syncthreads();
-    }
-    if (q >= Tn) return;
-    const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
-    T* orow = out + (base + q) * d + h * 64;
-#pragma unroll
-    for (int db = 0; db < 2; db++)
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-            T v4[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) v4[j] = (T)(oacc[db][rr * 4 + j] * inv);
-            *(uint2*)(orow + db * 32 + rr * 8 + 4 * hh) = *(const uint2*)v4;
-        }
-}
-
-// ------------------------------------------------------------------------------------------------
-// attn_enc2_kernel software-pipelined across key tiles (variant 3 of whisper_mi355x_bench_attn_encoder;
-// measured slower, kept bit-identical under test): iteration t issues the
-// score MFMAs of tile t+1 first, then runs the softmax of tile t and its P.V MFMAs, so a wave has
-// independent MFMA work in flight under its exponentials instead of alternating MFMA-only and
-// VALU-only phases in lockstep with its SIMD partner. K runs one tile ahead of V in the same two LDS
-// slots each: iteration t reads K(t+1) and V(t) and fills K(t+2), V(t+1). Every per-element operation
-// and its order is attn_enc2_kernel's, so the outputs are bit-identical.
-template <typename T>
-__global__ void __launch_bounds__(512) attn_enc3_kernel(const T* __restrict__ qkv, T* __restrict__ out, int Tn, int d) {
-    typedef typename Frag<T>::type FT;
-    typedef short v4s __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) v4s* lds_v4s_t;
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const int qb = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int hh = lane >> 5, ql = lane & 31;
-    const long base = (long)b * Tn;
-    const int ld = 3 * d;
-    __shared__ u32x4 Ks[2][64 * 8];
-    __shared__ u32x4 Vs[2][64 * 8];
-    const u32x4 zero = {0, 0, 0, 0};
-
-    const int q = qb * 256 + wave * 32 + ql;
-    FT qf[4];
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const u32x4 v = q < Tn ? *(const u32x4*)(qkv + (base + q) * ld + h * 64 + s * 16 + hh * 8) : zero;
-        qf[s] = __builtin_bit_cast(FT, v);
-    }
-    const int skey = tid >> 3, sch = tid & 7;
-    const int k_slot = skey * 8 + (sch ^ ((skey >> 1) & 7));
-    const int v_slot = skey * 8 + (sch ^ (((skey >> 1) & 1) << 2));
-    auto load_k = [&](int kt) -> u32x4 {
-        const int kg = kt * 64 + skey;
-        return kg < Tn ? *(const u32x4*)(qkv + (base + kg) * ld + d + h * 64 + sch * 8) : zero;
-    };
-    auto load_v = [&](int kt) -> u32x4 {
-        const int kg = kt * 64 + skey;
-        return kg < Tn ? *(const u32x4*)(qkv + (base + kg) * ld + 2 * d + h * 64 + sch * 8) : zero;
-    };
-    const int tg = (lane >> 4) & 1, tq = (lane & 15) >> 2, tp = lane & 3;
-    int vbase[2];
-#pragma unroll
-    for (int db = 0; db < 2; db++) {
-        const int ch = db * 4 + tg * 2 + (tp >> 1);
-        vbase[db] = (4 * hh + tq) * 128 + 16 * (ch ^ (((tq >> 1) & 1) << 2)) + 8 * (tp & 1);
-    }
-    const int n_kt = (Tn + 63) / 64;
-    // S^T of tile kt from K slot ks, masked past Tn
-    auto scores = [&](int kt, int ks, f32x16* sacc) {
-#pragma unroll
-        for (int kb = 0; kb < 2; kb++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) sacc[kb][r] = 0.0f;
-            const int key = kb * 32 + ql;
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                const FT kf = __builtin_bit_cast(FT, Ks[ks][key * 8 + ((s * 2 + hh) ^ ((key >> 1) & 7))]);
-                sacc[kb] = mfma32x32x16(kf, qf[s], sacc[kb]);
-            }
-        }
-        if (kt * 64 + 64 > Tn) {
-#pragma unroll
-            for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int key = kt * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    if (key >= Tn) sacc[kb][r] = -INFINITY;
-                }
-        }
-    };
-
-    f32x16 oacc[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) oacc[i][r] = 0.0f;
-    float m_run = -INFINITY, l_run = 0.0f;
-    const float c = 0.125f * 1.44269504088896340736f;
-
-    // prologue: K(0), V(0) -> slot 0, K(1) -> K slot 1; S(0)
-    Ks[0][k_slot] = load_k(0);
-    Vs[0][v_slot] = load_v(0);
-    if (n_kt > 1) Ks[1][k_slot] = load_k(1);
-    __syncthreads();
-    f32x16 scur[2];
-    scores(0, 0, scur);
-    __syncthreads();  // every wave has read K slot 0 before iteration 0 refills it with K(2)
-    for (int t = 0; t < n_kt; t++) {
-        const int cur = t & 1;
-        const bool more1 = t + 1 < n_kt, more2 = t + 2 < n_kt;
-        u32x4 nk = zero, nv = zero;
-        if (more2) nk = load_k(t + 2);
-        if (more1) nv = load_v(t + 1);
-        f32x16 snext[2];
-        if (more1) scores(t + 1, cur ^ 1, snext);
-        // softmax of tile t (attn_enc2_kernel's operations, same order)
-        float mx = scur[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) mx = fmaxf(mx, scur[kb][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx * c);
-        const bool moved = __builtin_amdgcn_ballot_w64(m_new != m_run) != 0;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        m_run = m_new;
-        const f2 c2 = {c, c}, nm2 = {-m_new, -m_new};
-        FT pf[4];
-        f2 ls2 = {0.0f, 0.0f};
-#pragma unroll
-        for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-            for (int sp = 0; sp < 2; sp++)
-#pragma unroll
-                for (int j = 0; j < 8; j += 2) {
-                    const f2 x = {scur[kb][sp * 8 + j], scur[kb][sp * 8 + j + 1]};
-                    const f2 e = __builtin_elementwise_fma(x, c2, nm2);
-                    const f2 p = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-                    ls2 += p;
-                    pf[kb * 2 + sp][j] = (T)p.x;
-                    pf[kb * 2 + sp][j + 1] = (T)p.y;
-                }
-        l_run = l_run * alpha + (ls2.x + ls2.y);
-        if (moved) {
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) oacc[i][r] *= alpha;
-        }
-        const char* vimg = (const char*)Vs[cur];
-#pragma unroll
-        for (int db = 0; db < 2; db++)
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                const int r0 = (s >> 1) * 32 + (s & 1) * 16;
-                const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t)(vimg + vbase[db] + r0 * 128));
-                const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t)(vimg + vbase[db] + (r0 + 8) * 128));
-                const FT vf = __builtin_bit_cast(FT, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-                oacc[db] = mfma32x32x16(vf, pf[s], oacc[db]);
-            }
-        if (more2) Ks[cur][k_slot] = nk;
-        if (more1) Vs[cur ^ 1][v_slot] = nv;
-        __syncthreads();
-        if (more1) {
-            scur[0] = snext[0];
-            scur[1] = snext[1];
-        }
     }
     if (q >= Tn) return;
     const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
@@ -716,9 +423,8 @@ __global__ void __launch_bounds__(1024) attn_cross_step_wide_kernel(const DecSla
 // [0, pos) from the cache plus the fresh key from registers. Scores: 8 lanes per key row (16 B
 // each), U rows in flight per lane group; softmax and P.V reductions are wave shuffles.
 // Sums over the 8 lanes of a key row by DPP (quad xor 1, quad xor 2, half-row mirror): the same
-// bits as the xor butterfly, without LDS round trips. NT: the cached K and V rows (read once per
-// step) by non-temporal loads.
-template <typename T, int HPB, bool NT>
+// bits as the xor butterfly, without LDS round trips.
+template <typename T, int HPB>
 __global__ void __launch_bounds__(64 * HPB) attn_self_step_kernel(const DecSlabs sl, T* __restrict__ cache,
                                                                   const int* __restrict__ slot,
                                                                   const int* __restrict__ pos_arr, int L, int layer,
@@ -742,7 +448,7 @@ __global__ void __launch_bounds__(64 * HPB) attn_self_step_kernel(const DecSlabs
         for (int u = 0; u < U; u++) {
             const int t = t0 + 8 * u;
             const u32x4* src = (const u32x4*)(K + (long)t * 64 + lane8 * 8);
-            raw[u] = t < pos ? (NT ? __builtin_nontemporal_load(src) : *src) : zero;
+            raw[u] = t < pos ? *src : zero;
         }
     };
     kload(grp);
@@ -832,7 +538,7 @@ __global__ void __launch_bounds__(64 * HPB) attn_self_step_kernel(const DecSlabs
         for (int u = 0; u < U; u++) {
             const int t = t0 + 8 * u;
             const u32x4* src = (const u32x4*)(V + (long)t * 64 + lane8 * 8);
-            vraw[u] = t < pos ? (NT ? __builtin_nontemporal_load(src) : *src) : zero;
+            vraw[u] = t < pos ? *src : zero;
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
@@ -870,8 +576,8 @@ __global__ void __launch_bounds__(64 * HPB) attn_self_step_kernel(const DecSlabs
 // all 64 queries (the one-query-per-workgroup kernel above re-reads the clip's whole cache per token).
 // Two passes keep ggml's soft_max order (normalise, then round P to the f16 src1 of P.V): pass 1
 // S = Q.K^T by MFMA with an online row max and sum; pass 2 S again, P = (T)(exp(S - max) / sum),
-// O += P.V by MFMA (K tiles row-major and V tiles transposed in XOR-swizzled LDS images, as
-// attn_enc_kernel). Rows of a tile must have non-decreasing n_kv (positions increase).
+// O += P.V by MFMA (K tiles row-major and V tiles transposed in XOR-swizzled LDS images, both
+// products v_mfma_f32_16x16x32 with ds_read_b128 operand fetches). Rows of a tile must have non-decreasing n_kv (positions increase).
 template <typename T>
 __global__ void __launch_bounds__(256) attn_prefill_kernel(const T* __restrict__ q, int q_stride, const T* __restrict__ cache,
                                                            const int* __restrict__ slot, const int* __restrict__ n_kv_arr,
@@ -1033,43 +739,25 @@ static bool attn_enc_xcd() {
 
 void launch_attn_encoder(DType dt, const void* qkv, void* out, int B, int Tn, int d, int H, hipStream_t st,
                          int variant_arg) {
-    // variant 6 (attn_enc2_kernel, 128 VGPRs, scalar softmax FMAs) unless a kernel benchmark asks for
-    // another (whisper_mi355x_bench_attn_encoder)
+    // variant 6 (attn_enc2_kernel<T, 4, false>: 128 VGPRs, scalar softmax FMAs) is production; 2 (the plain
+    // attn_enc2_kernel<T>) is the bitwise reference of the kernel test (whisper_mi355x_debug_attn_encoder)
     const int variant = variant_arg >= 0 ? variant_arg : 6;
-    if (variant == 3 && d == H * 64) {
-        dim3 grid(cdiv(Tn, 256), H, B);
-        if (dt == DType::F16) attn_enc3_kernel<half_t><<<grid, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
-        else attn_enc3_kernel<bf16_t><<<grid, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
-        return;
-    }
-    if (variant == 6 && d == H * 64) {
-        const int nqb = cdiv(Tn, 256);
-        if ((long)nqb * H * B % 8 == 0 && attn_enc_xcd()) {
-            const int G = nqb * H * B;
-            if (dt == DType::F16) attn_enc2_kernel<half_t, 4, false><<<G, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d, nqb, H);
-            else attn_enc2_kernel<bf16_t, 4, false><<<G, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d, nqb, H);
-            return;
-        }
-        dim3 grid(nqb, H, B);
-        if (dt == DType::F16) attn_enc2_kernel<half_t, 4, false><<<grid, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
-        else attn_enc2_kernel<bf16_t, 4, false><<<grid, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
-        return;
-    }
-    if (variant == 5 && d == H * 64) {
-        dim3 grid(cdiv(Tn, 256), H, B);
-        if (dt == DType::F16) attn_enc2_kernel<half_t, 4><<<grid, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
-        else attn_enc2_kernel<bf16_t, 4><<<grid, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
-        return;
-    }
-    if (variant == 2 && d == H * 64) {
-        dim3 grid(cdiv(Tn, 256), H, B);
+    if (d != H * 64 || (variant != 2 && variant != 6)) WM_FAIL("encoder attention: d %d != 64 x %d heads, or variant %d", d, H, variant);
+    const int nqb = cdiv(Tn, 256);
+    const dim3 grid(nqb, H, B);
+    if (variant == 2) {
         if (dt == DType::F16) attn_enc2_kernel<half_t><<<grid, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
         else attn_enc2_kernel<bf16_t><<<grid, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
         return;
     }
-    dim3 grid(cdiv(Tn, 64), H, B);
-    if (dt == DType::F16) attn_enc_kernel<half_t><<<grid, 256, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
-    else attn_enc_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
+    if ((long)nqb * H * B % 8 == 0 && attn_enc_xcd()) {
+        const int G = nqb * H * B;
+        if (dt == DType::F16) attn_enc2_kernel<half_t, 4, false><<<G, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d, nqb, H);
+        else attn_enc2_kernel<bf16_t, 4, false><<<G, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d, nqb, H);
+        return;
+    }
+    if (dt == DType::F16) attn_enc2_kernel<half_t, 4, false><<<grid, 512, 0, st>>>((const half_t*)qkv, (half_t*)out, Tn, d);
+    else attn_enc2_kernel<bf16_t, 4, false><<<grid, 512, 0, st>>>((const bf16_t*)qkv, (bf16_t*)out, Tn, d);
 }
 
 // WHISPER_MI355X_XWIDE_MAX (default 8, read per call): decode steps of up to this many clips use the
@@ -1110,7 +798,7 @@ void launch_attn_self_step(DType dt, const DecSlabs& sl, void* cache, const int*
     const int hpb = want >= 4 && H % 4 == 0 ? 4 : want >= 2 && H % 2 == 0 ? 2 : 1;
     // default-policy K/V reads (non-temporal measured 3048-3053 vs 3050-3057 audio-s/s, not kept)
 #define WM_SELF(TT, HB) \
-    attn_self_step_kernel<TT, HB, false><<<dim3(n, H / HB), 64 * HB, 0, st>>>(sl, (TT*)cache, slot, pos, L, layer, H, ctx, d, (TT*)out)
+    attn_self_step_kernel<TT, HB><<<dim3(n, H / HB), 64 * HB, 0, st>>>(sl, (TT*)cache, slot, pos, L, layer, H, ctx, d, (TT*)out)
 #define WM_SELF_H(TT) \
     do { if (hpb == 4) WM_SELF(TT, 4); else if (hpb == 2) WM_SELF(TT, 2); else WM_SELF(TT, 1); } while (0)
     if (dt == DType::F16) WM_SELF_H(half_t);

@@ -17,12 +17,22 @@
 //
 // Roofline: MFMA-bound for the encoder/cross-KV/prefill shapes (M = B*1500), HBM-bound on the
 // weights for decode steps (M = number of active sequences).
+//
+// The GEMM kernels, and what launch_t runs them for:
+//   gemm8p_kernel      256x256 phase-interleaved LDS-DMA tiles: the big shapes (encoder, cross K/V, prefill)
+//   gemm8p_mx_kernel   the same schedule on e4m3 operands with row scales (launch_gemm_fp8)
+//   gemm_glds_kernel   128x128 LDS-DMA tiles: big shapes the 256^2 rule leaves out (and variant 1)
+//   gemm_dec_kernel    decode steps and small prefills: 32/64/128 rows x 64 columns x one K chunk, split-K
+//   gemm_small_kernel  decode steps of <= 32 clips, no split-K slab (launch_gemm_small)
+//   gemm_kernel        register-staged fallback for every other shape (K % 64 != 0, no workspace, variant 0)
+// with splitk_reduce_kernel / splitk_reduce_resid_ln_kernel / splitk_reduce_resid_ln4_kernel after the split ones.
 #include <mutex>
 #include "../common.h"
 #include "../kernels.h"
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace wm {
@@ -104,6 +114,46 @@ __device__ __forceinline__ float gelu_formula(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __expf(-u));
 }
 
+// Element index into a K/V cache [slot][L][2][H][ctx][64].
+__device__ __forceinline__ long cache_index(const GemmArgs& g, long slot, int l, int kv, int h, long t, int dh) {
+    return ((((slot * g.L + l) * 2 + kv) * g.H + h) * g.ctx + t) * 64 + dh;
+}
+// Where output (m, n) of a K/V-cache epilogue goes: the column part (layer, K or V, head, dim; whether the
+// value is multiplied by g.scale first) decoded from n once, then at(g, m) = the element pointer of row m.
+// gemm8p_kernel's whole-row stores keep n over a loop of rows and fold the column part themselves:
+// index(g, 0, 0) + slot * cache_index(g, 1, 0, 0, 0, 0, 0) + 64 t.
+// EPI_CROSSKV: row m = (clip, audio position t); the N columns are [layer][K | V][d], from layer g.layer on.
+template <typename T>
+struct CrossKvDst {
+    int l, kv, h, dh;
+    bool scaled;  // K columns
+    __device__ __forceinline__ CrossKvDst(const GemmArgs& g, int n)
+        : l(g.layer + n / (2 * g.d)), kv((n / g.d) & 1), h((n % g.d) >> 6), dh(n & 63), scaled(kv == 0) {}
+    __device__ __forceinline__ long index(const GemmArgs& g, long slot, long t) const { return cache_index(g, slot, l, kv, h, t, dh); }
+    __device__ __forceinline__ T* at(const GemmArgs& g, int m) const {
+        const int b = m / g.ctx, t = m % g.ctx;
+        return (T*)g.cache + index(g, g.row_slot[b], t);
+    }
+};
+// EPI_QKV_DEC: the columns are q | k | v of layer g.layer; q goes to out, k and v of row m into the self
+// cache of clip g.row_slot[m] at position g.row_pos[m].
+template <typename T>
+struct QkvDecDst {
+    int part, n;  // part: 0 q, 1 k, 2 v
+    bool scaled;  // q and k columns
+    __device__ __forceinline__ QkvDecDst(const GemmArgs& g, int n_) : part(n_ / g.d), n(n_), scaled(part <= 1) {}
+    __device__ __forceinline__ long index(const GemmArgs& g, long slot, long t) const {
+        const int nn = n - part * g.d;
+        return cache_index(g, slot, g.layer, part == 2, nn >> 6, t, nn & 63);
+    }
+    __device__ __forceinline__ T* at(const GemmArgs& g, int m) const {
+        if (part == 0) return (T*)g.out + (long)m * g.ldo + n;
+        return (T*)g.cache + index(g, g.row_slot[m], g.row_pos[m]);
+    }
+};
+template <int EPI, typename T>
+using CacheDst = typename std::conditional<EPI == EPI_CROSSKV, CrossKvDst<T>, QkvDecDst<T>>::type;
+
 template <int EPI, typename T, bool NOB = false>
 __device__ __forceinline__ void epilogue(const GemmArgs& g, int m, int n, float v) {
     if (!NOB && g.bias) v = v + g.bias[n];
@@ -124,22 +174,16 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, int m, int n, float 
         ((float*)g.out)[(long)m * g.ldo + n] = gelu_tab(v) + g.pos[(long)(m % g.pos_rows) * g.N + n];
     } else if constexpr (EPI == EPI_F32) {
         ((float*)g.out)[(long)m * g.ldo + n] = v;
-    } else if constexpr (EPI == EPI_CROSSKV) {
-        const int b = m / g.ctx, t = m % g.ctx;
-        const int l = n / (2 * g.d), kv = (n / g.d) & 1, h = (n % g.d) >> 6, dh = n & 63;
-        if (kv == 0) v = v * g.scale;
-        const long slot = g.row_slot[b];
-        ((T*)g.cache)[((((slot * g.L + l) * 2 + kv) * g.H + h) * g.ctx + t) * 64 + dh] = (T)v;
-    } else if constexpr (EPI == EPI_QKV_DEC) {
-        const int part = n / g.d;
-        if (part == 0) {
-            ((T*)g.out)[(long)m * g.ldo + n] = (T)(v * g.scale);
-        } else {
-            const int kv = part - 1, nn = n - part * g.d, h = nn >> 6, dh = nn & 63;
-            if (kv == 0) v = v * g.scale;
-            const long slot = g.row_slot[m], pos = g.row_pos[m];
-            ((T*)g.cache)[((((slot * g.L + g.layer) * 2 + kv) * g.H + h) * g.ctx + pos) * 64 + dh] = (T)v;
+    } else if constexpr (EPI == EPI_CROSSKV || EPI == EPI_QKV_DEC) {
+        const CacheDst<EPI, T> c(g, n);
+        if constexpr (EPI == EPI_QKV_DEC) {
+            if (c.part == 0) {  // q first: the cache branch then decodes its head only where it runs (2 VGPRs)
+                *c.at(g, m) = (T)(v * g.scale);
+                return;
+            }
         }
+        if (c.scaled) v = v * g.scale;
+        *c.at(g, m) = (T)v;
     }
 }
 
@@ -176,11 +220,9 @@ __device__ __forceinline__ void epilogue16(const GemmArgs& g, int m, int n, floa
         float sc = 1.0f;
         T* dst;
         if constexpr (EPI == EPI_CROSSKV) {
-            const int b = m / g.ctx, t = m % g.ctx;
-            const int l = n / (2 * g.d), kv = (n / g.d) & 1, h = (n % g.d) >> 6, dh = n & 63;
-            if (kv == 0) sc = g.scale;
-            const long slot = g.row_slot[b];
-            dst = (T*)g.cache + ((((slot * g.L + l) * 2 + kv) * g.H + h) * g.ctx + t) * 64 + dh;
+            const CrossKvDst<T> c(g, n);
+            if (c.scaled) sc = g.scale;
+            dst = c.at(g, m);
         } else {
             if constexpr (EPI == EPI_STORE)
                 if (g.sc_div > 0 && ((n / g.sc_div) % g.sc_mod) < g.sc_lim) sc = g.scale;
@@ -438,152 +480,9 @@ __global__ void __launch_bounds__(256) gemm_glds_kernel(const GemmArgs g, const 
 }
 
 // 256x256x64 tiles, 8 waves (2 x 4), each wave 128x64 (8 x 4 MFMA 16x16x32 tiles, 128 accumulator
-// registers): twice the MFMA work per barrier of the 128x128 kernel and 0.375 LDS fragment reads
-// per MFMA. Same LDS-DMA staging, swizzle and XCD remap; 2 stages x 64 KiB LDS, one block per CU.
-// PIPE: fragment reads of the next k-step are issued under the current k-step's MFMAs (two
-// register sets), one barrier per K-tile placed between the two k-steps; the DMA of tile t+2 is
-// issued right after that barrier into the buffer tile t has just released.
-template <typename T, int EPI, bool PIPE>
-__global__ void __launch_bounds__(512) gemm256_kernel(const GemmArgs g, const int tiles_n) {
-    typedef typename Frag<T>::type FT;
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
-    constexpr int BM = 256, BN = 256, BK = 64;
-    __shared__ u32x4 lds[2][(BM + BN) * 8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rr = nwg & 7;
-    const int wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (orig >> 3);
-    const int m0 = (wgid / tiles_n) * BM, n0 = (wgid % tiles_n) * BN;
-    const T* A = (const T*)g.A;
-    const T* B = (const T*)g.B;
-    // A tile = 32 pieces of 8 rows x 128 B; 8 waves x 4 pieces. Same for B.
-    const T* a_src[4];
-    const T* b_src[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int r = (wave * 4 + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        const int m = min(m0 + r, g.M - 1);
-        a_src[i] = A + (m / g.a_rpb) * g.a_bstride + (m % g.a_rpb) * g.a_rstride + c * 8;
-        const int n = min(n0 + r, g.N - 1);
-        b_src[i] = B + (long)n * g.K + c * 8;
-    }
-    auto issue = [&](int stage, int kt) {
-        const int kb = kt * BK;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            __builtin_amdgcn_global_load_lds((const void*)(a_src[i] + kb), (lds_ptr_t)&lds[stage][(wave * 4 + i) * 64], 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            __builtin_amdgcn_global_load_lds((const void*)(b_src[i] + kb), (lds_ptr_t)&lds[stage][BM * 8 + (wave * 4 + i) * 64],
-                                             16, 0, 0);
-    };
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int nk = g.K / BK;
-    if constexpr (PIPE) {
-        auto read_frags = [&](int buf, int s, FT (&af)[8], FT (&bfr)[4]) {
-            const int ch = s * 4 + (lane >> 4);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int row = wn * 64 + j * 16 + (lane & 15);
-                bfr[j] = __builtin_bit_cast(FT, lds[buf][BM * 8 + row * 8 + (ch ^ ((row >> 1) & 7))]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int row = wm * 128 + i * 16 + (lane & 15);
-                af[i] = __builtin_bit_cast(FT, lds[buf][row * 8 + (ch ^ ((row >> 1) & 7))]);
-            }
-        };
-        auto mfmas = [&](const FT (&af)[8], const FT (&bfr)[4]) {
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[i][j] = mfma16x16x32(af[i], bfr[j], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-        };
-        FT a0[8], b0[4], a1[8], b1[4];
-        issue(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (nk > 1) issue(1, 1);
-        read_frags(0, 0, a0, b0);
-        for (int kt = 0; kt < nk; kt++) {
-            const int cur = kt & 1;
-            read_frags(cur, 1, a1, b1);  // k-step 1 of this tile, under k-step 0's MFMAs
-            mfmas(a0, b0);
-            // tile kt+1 landed (this wave's DMA), every wave done reading tile kt
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            if (kt + 2 < nk) issue(cur, kt + 2);
-            if (kt + 1 < nk) read_frags(cur ^ 1, 0, a0, b0);  // next tile's k-step 0, under k-step 1
-            mfmas(a1, b1);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    } else {
-    issue(0, 0);
-    for (int kt = 0; kt < nk; kt++) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) {
-            issue(cur ^ 1, kt + 1);
-            asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            FT af[8], bfr[4];
-            const int ch = s * 4 + (lane >> 4);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int row = wn * 64 + j * 16 + (lane & 15);
-                bfr[j] = __builtin_bit_cast(FT, lds[cur][BM * 8 + row * 8 + (ch ^ ((row >> 1) & 7))]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int row = wm * 128 + i * 16 + (lane & 15);
-                af[i] = __builtin_bit_cast(FT, lds[cur][row * 8 + (ch ^ ((row >> 1) & 7))]);
-            }
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[i][j] = mfma16x16x32(af[i], bfr[j], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-    }
-    // epilogue: each wave transposes its 128x64 tile through LDS 16 rows at a time so every lane
-    // owns 16 consecutive columns of one row (16-byte stores instead of 4-byte column stores)
-    constexpr int LDW = 68;  // padded f32 row stride of the staging image
-    float* stg = (float*)&lds[0][0] + wave * 16 * LDW;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) stg[((lane >> 4) * 4 + r) * LDW + j * 16 + (lane & 15)] = acc[i][j][r];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        const int row = lane >> 2, c0 = (lane & 3) * 16;
-        float v[16];
-#pragma unroll
-        for (int k = 0; k < 16; k += 4) {
-            const float4 x = *(const float4*)(stg + row * LDW + c0 + k);
-            v[k] = x.x; v[k + 1] = x.y; v[k + 2] = x.z; v[k + 3] = x.w;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        const int m = m0 + wm * 128 + i * 16 + row, n = n0 + wn * 64 + c0;
-        if (m < g.M && n < g.N) epilogue16<EPI, T>(g, m, n, v);
-    }
-}
-
-// 256x256x64 tiles, 8 waves (2 x 4), each wave 128x64 — the phase-interleaved schedule of the
-// guide's 256^2 8-phase template, restated for this engine's operand layout. A K-tile is four
+// registers, 0.375 LDS fragment reads per MFMA; 2 stages x 64 KiB LDS, one block per CU) — the
+// phase-interleaved schedule of the guide's 256^2 8-phase template, restated for this engine's operand
+// layout. LDS-DMA staging, swizzle and XCD remap as gemm_glds_kernel. A K-tile is four
 // phases, one per C quadrant of the wave (64 rows x 32 columns x K 64 = 16 MFMAs): each phase reads
 // the register subtile it needs (P1: B cols 0-31 + A rows 0-63; P2: B cols 32-63; P3: A rows
 // 64-127; P4: none — A rows 64-127 and B cols 0-31 are still in registers), then a barrier, the
@@ -794,26 +693,16 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(const GemmArgs g, const int
     // position, consecutive positions for a clip's prompt) takes the same map; it went per element before.
     bool xdone = false;
     if constexpr (EPI == EPI_CROSSKV || EPI == EPI_QKV_DEC) {
-        if (full && (EPI == EPI_CROSSKV || ((((uintptr_t)g.out) & 15) == 0 && (g.ldo & 7) == 0 && g.d % 64 == 0))) {
+        if (full && g.d % 64 == 0 && (EPI == EPI_CROSSKV || ((((uintptr_t)g.out) & 15) == 0 && (g.ldo & 7) == 0))) {
             const int r8 = lane >> 3, c8 = (lane & 7) * 8, n = nb + c8;
             float b8[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) b8[k] = g.bias ? g.bias[n + k] : 0.0f;
-            float sc;
-            long colpart, sstride;
-            int part = 0;
-            if constexpr (EPI == EPI_CROSSKV) {
-                const int l = g.layer + n / (2 * g.d), kv = (n / g.d) & 1, hh = (n % g.d) >> 6, dh = n & 63;
-                sc = kv == 0 ? g.scale : 1.0f;
-                colpart = (((long)l * 2 + kv) * g.H + hh) * g.ctx * 64 + dh;
-                sstride = (long)g.L * 2 * g.H * g.ctx * 64;
-            } else {
-                part = n / g.d;  // 0 q, 1 k, 2 v
-                const int nn = n - part * g.d, hh = nn >> 6, dh = nn & 63;
-                sc = part <= 1 ? g.scale : 1.0f;
-                colpart = (((long)g.layer * 2 + (part == 2)) * g.H + hh) * g.ctx * 64 + dh;
-                sstride = (long)g.L * 2 * g.H * g.ctx * 64;
-            }
+            const CacheDst<EPI, T> c(g, n);
+            const float sc = c.scaled ? g.scale : 1.0f;
+            const long colpart = c.index(g, 0, 0), sstride = cache_index(g, 1, 0, 0, 0, 0, 0);
+            bool qcol = false;  // q columns go to out, always scaled (as the element form)
+            if constexpr (EPI == EPI_QKV_DEC) qcol = c.part == 0;
 #pragma unroll
             for (int i = 0; i < 8; i++) {
 #pragma unroll
@@ -841,8 +730,7 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(const GemmArgs g, const int
                     for (int k = 0; k < 8; k++) {
                         float v = x[h2][k];
                         if (g.bias) v = v + b8[k];
-                        if (EPI == EPI_QKV_DEC && part == 0) v = v * sc;  // (q: always scaled, as the element form)
-                        else if (sc != 1.0f) v = v * sc;
+                        if (qcol || sc != 1.0f) v = v * sc;
                         o[k] = (T)v;
                     }
                     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
@@ -850,8 +738,8 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(const GemmArgs g, const int
                     if constexpr (EPI == EPI_CROSSKV) {
                         const int bb = m / g.ctx, t = m - bb * g.ctx;
                         dst = (T*)g.cache + (long)g.row_slot[bb] * sstride + colpart + (long)t * 64;
-                    } else if (part == 0) {
-                        dst = (T*)g.out + (long)m * g.ldo + n;
+                    } else if (qcol) {
+                        dst = c.at(g, m);
                     } else {
                         dst = (T*)g.cache + (long)g.row_slot[m] * sstride + colpart + (long)g.row_pos[m] * 64;
                     }
@@ -926,25 +814,17 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(const GemmArgs g, const int
                 }
                 continue;
             }
-        } else if constexpr (EPI == EPI_STORE || EPI == EPI_GELU || EPI == EPI_GELU_F || EPI == EPI_CROSSKV) {
+        } else if constexpr (EPI == EPI_STORE || EPI == EPI_GELU || EPI == EPI_GELU_F) {
             typedef uint32_t u4 __attribute__((ext_vector_type(4)));
             if (full) {
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
-                    const int n = nb + 32 * h + 8 * q;  // 8 columns of one head (64-aligned blocks)
+                    const int n = nb + 32 * h + 8 * q;
                     float sc = 1.0f;
-                    T* dst;
-                    if constexpr (EPI == EPI_CROSSKV) {
-                        const int bb = m / g.ctx, t = m % g.ctx;
-                        const int l = n / (2 * g.d), kv = (n / g.d) & 1, hh = (n % g.d) >> 6, dh = n & 63;
-                        if (kv == 0) sc = g.scale;
-                        dst = (T*)g.cache + ((((long)g.row_slot[bb] * g.L + l) * 2 + kv) * g.H + hh) * g.ctx * 64 + (long)t * 64 + dh;
-                    } else {
-                        if constexpr (EPI == EPI_STORE)
-                            if (g.sc_div > 0 && ((n / g.sc_div) % g.sc_mod) < g.sc_lim) sc = g.scale;
-                        const long orow = (m / g.o_rpb) * g.o_bstride + (m % g.o_rpb) + g.o_off;
-                        dst = (T*)g.out + orow * g.ldo + n;
-                    }
+                    if constexpr (EPI == EPI_STORE)
+                        if (g.sc_div > 0 && ((n / g.sc_div) % g.sc_mod) < g.sc_lim) sc = g.scale;
+                    const long orow = (m / g.o_rpb) * g.o_bstride + (m % g.o_rpb) + g.o_off;
+                    T* dst = (T*)g.out + orow * g.ldo + n;
                     if ((((uintptr_t)dst) & 15) == 0) {
                         T o[8];
 #pragma unroll
@@ -964,7 +844,8 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(const GemmArgs g, const int
                 continue;
             }
         }
-        // edge tiles (columns past N, unaligned rows): per element, the bias already added
+        // edge tiles (columns past N, unaligned rows; the cache epilogues whenever the whole-row path above
+        // did not apply): per element, the bias already added
 #pragma unroll
         for (int k = 0; k < 16; k++)
             if (colk(k) < g.N) epilogue<EPI, T, true>(g, m, colk(k), v[k]);
@@ -1354,8 +1235,8 @@ __global__ void __launch_bounds__(256) gemm_dec_kernel(const GemmArgs g, const i
         }
 }
 
-// debug/tuning override: -1 auto, 0 register-staged, 1 LDS-DMA 128^2, 2 LDS-DMA 256^2, 3 same,
-// pipelined, 4 256^2 phase-interleaved (the auto choice for big GEMMs)
+// debug/tuning override: -1 auto, 0 register-staged, 1 LDS-DMA 128^2 in place of 256^2, >= 2 the 256^2
+// phase-interleaved kernel (the auto choice for big GEMMs) wherever the shape is big
 int g_gemm_variant = -1;
 unsigned long long* g_gemm_stamps = nullptr;
 
@@ -1369,7 +1250,7 @@ static int dec_bm_min() {
     return g_dec_bm > 0 ? g_dec_bm : v;
 }
 template <typename T, int EPI, bool SPLIT, bool W8>
-static void launch_dec(const GemmArgs& g, int tiles, int splits, int kc, hipStream_t st) {
+static void launch_dec_w(const GemmArgs& g, int tiles, int splits, int kc, hipStream_t st) {
     if (g.M <= 32 && dec_bm_min() <= 32) {
         gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 32><<<dim3(tiles, 1, splits), 256, 0, st>>>(g, kc);
     } else if (g.M <= 64 && dec_bm_min() <= 64) {
@@ -1380,6 +1261,12 @@ static void launch_dec(const GemmArgs& g, int tiles, int splits, int kc, hipStre
         // profiles/r06_bm_m64_ab_*.json) though some isolated shapes gained (xq 11.9 -> 10.7 us)
         gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 128><<<dim3(tiles, cdiv(g.M, 128), splits), 256, 0, st>>>(g, kc);
     }
+}
+// W8: the weights are e4m3 bytes (g.w8_scale set)
+template <typename T, int EPI, bool SPLIT>
+static void launch_dec(const GemmArgs& g, int tiles, int splits, int kc, hipStream_t st) {
+    if (g.w8_scale) launch_dec_w<T, EPI, SPLIT, true>(g, tiles, splits, kc, st);
+    else launch_dec_w<T, EPI, SPLIT, false>(g, tiles, splits, kc, st);
 }
 
 template <typename T, int EPI>
@@ -1864,10 +1751,25 @@ static int dec_splits_for(int tiles, int nk) {
     while (tiles * (splits + 1) <= 256 && splits < 12 && (splits + 1) * 2 <= nk) splits++;
     return splits;
 }
+// The split plan of a gemm_dec_kernel launch (K % 64 == 0): dec_splits_for's count (or the override) as
+// chunks of whole K-tiles, kc elements each, and the number of chunks that makes. splits = 0: the slabs do
+// not fit the workspace.
+struct DecPlan { int splits, kc; };
+static DecPlan dec_plan(int N, int K, int M, long ws_elems) {
+    const int nk = K / 64;
+    int splits = dec_splits_for(cdiv(N, 64), nk);
+    if (dec_splits_override() > 0) splits = std::min(dec_splits_override(), nk);
+    const int kc = cdiv(nk, splits) * 64;
+    splits = cdiv(K, kc);
+    if ((long)splits * M * N > ws_elems) return {0, 0};
+    return {splits, kc};
+}
 
+// ln4: take the 4-columns-per-thread kernel where it applies (the register-staged path below never did, and
+// the two kernels' LayerNorm sums associate differently, so it keeps its choice)
 template <typename T>
-static void launch_reduce_resid_ln(const GemmArgs& g, int splits, hipStream_t st) {
-    if (g.N % 4 == 0 && g.N <= 4096 && splits <= 16) {
+static void launch_reduce_resid_ln(const GemmArgs& g, int splits, hipStream_t st, bool ln4 = true) {
+    if (ln4 && g.N % 4 == 0 && g.N <= 4096 && splits <= 16) {
         const int threads = cdiv(g.N / 4, 64) * 64;
         splitk_reduce_resid_ln4_kernel<T><<<g.M, threads, 0, st>>>(g, splits);
         return;
@@ -1911,13 +1813,9 @@ static void launch_t(const GemmArgs& g, hipStream_t st) {
                         (g_gemm_variant < 0 && (g.N % 256 == 0 || g.N >= 1024) && g.M >= 1024);
     if ((long)g.M * g.N >= 256L * 128 * 128 && g.K % 64 == 0 && big256) {
         const int tn = cdiv(g.N, 256);
-        if (g_gemm_variant == 2) gemm256_kernel<T, EPI, false><<<tn * cdiv(g.M, 256), 512, 0, st>>>(g, tn);
-        else if (g_gemm_variant == 3) gemm256_kernel<T, EPI, true><<<tn * cdiv(g.M, 256), 512, 0, st>>>(g, tn);
-        else {
-            GemmArgs ga = g;
-            ga.stamps = g_gemm_stamps;
-            gemm8p_kernel<T, EPI><<<tn * cdiv(g.M, 256), 512, 0, st>>>(ga, tn, gemm_group_m(tn));
-        }
+        GemmArgs ga = g;
+        ga.stamps = g_gemm_stamps;
+        gemm8p_kernel<T, EPI><<<tn * cdiv(g.M, 256), 512, 0, st>>>(ga, tn, gemm_group_m(tn));
         return;
     }
     if ((long)g.M * g.N >= 256L * 128 * 128 && g.K % 64 == 0 && g_gemm_variant != 0) {
@@ -1939,27 +1837,19 @@ static void launch_t(const GemmArgs& g, hipStream_t st) {
         // K-tiles measured faster in isolation, 9.6 vs 10.4 us at N = K = 1280, but not in the decode
         // step: 82.0 vs 81.6 us of GEMM + reduce per layer.)
         const int tiles = cdiv(g.N, 64);
-        int splits = dec_splits_for(tiles, nk);
-        if (dec_splits_override() > 0) splits = std::min(dec_splits_override(), nk);
+        const DecPlan p = dec_plan(g.N, g.K, g.M, g.splitk_ws_elems);
         // unsplit at M <= 64 (the logits GEMM of a small batch): the 64-row register-staged kernel
         // below wastes less of its tile (measured 23 vs 51 us at M = 16, N = 51866)
-        const bool small_unsplit = splits == 1 && !fused_ln && g.M <= 64 && !g.w8_scale;
-        if (g.w8_scale && (long)splits * g.M * g.N > g.splitk_ws_elems) WM_FAIL("e4m3 decode GEMM: split-K workspace too small");
-        if ((long)splits * g.M * g.N <= g.splitk_ws_elems && !small_unsplit) {
-            const int kc = cdiv(nk, splits) * 64;
-            splits = cdiv(g.K, kc);
-            if (splits == 1 && !fused_ln) {
-                if (g.w8_scale) launch_dec<T, EPI, false, true>(g, tiles, 1, kc, st);
-                else launch_dec<T, EPI, false, false>(g, tiles, 1, kc, st);
+        const bool small_unsplit = p.splits == 1 && !fused_ln && g.M <= 64 && !g.w8_scale;
+        if (g.w8_scale && !p.splits) WM_FAIL("e4m3 decode GEMM: split-K workspace too small");
+        if (p.splits && !small_unsplit) {
+            if (p.splits == 1 && !fused_ln) {
+                launch_dec<T, EPI, false>(g, tiles, 1, p.kc, st);
                 return;
             }
-            if (g.w8_scale) launch_dec<T, EPI, true, true>(g, tiles, splits, kc, st);
-            else launch_dec<T, EPI, true, false>(g, tiles, splits, kc, st);
-            if (fused_ln) {
-                launch_reduce_resid_ln<T>(g, splits, st);
-            } else {
-                launch_splitk_reduce<T, EPI>(g, splits, st);
-            }
+            launch_dec<T, EPI, true>(g, tiles, p.splits, p.kc, st);
+            if (fused_ln) launch_reduce_resid_ln<T>(g, p.splits, st);
+            else launch_splitk_reduce<T, EPI>(g, p.splits, st);
             return;
         }
     }
@@ -1976,14 +1866,8 @@ static void launch_t(const GemmArgs& g, hipStream_t st) {
             dim3 grid(tiles, 1, splits);
             if (BM == 64) gemm_kernel<T, 64, 64, 2, 2, EPI, true><<<grid, 256, 0, st>>>(g, kc);
             else gemm_kernel<T, 128, 64, 2, 2, EPI, true><<<grid, 256, 0, st>>>(g, kc);
-            if (fused_ln) {
-                const int npt = cdiv(g.N, 256);
-                if (npt <= 4) splitk_reduce_resid_ln_kernel<T, 4><<<g.M, 256, 0, st>>>(g, splits);
-                else if (npt <= 8) splitk_reduce_resid_ln_kernel<T, 8><<<g.M, 256, 0, st>>>(g, splits);
-                else WM_FAIL("fused LN width %d > 2048", g.N);
-            } else {
-                launch_splitk_reduce<T, EPI>(g, splits, st);
-            }
+            if (fused_ln) launch_reduce_resid_ln<T>(g, splits, st, false);
+            else launch_splitk_reduce<T, EPI>(g, splits, st);
         } else {
             dim3 grid(tiles, 1);
             if (BM == 64) gemm_kernel<T, 64, 64, 2, 2, EPI, false><<<grid, 256, 0, st>>>(g, g.K);
@@ -2027,17 +1911,10 @@ static void launch_dt(int epi, const GemmArgs& g, hipStream_t st) {
 template <typename T>
 static int launch_partials_t(const GemmArgs& g, hipStream_t st) {
     if (!g.splitk_ws || g.M > 128 || g.K % 64 != 0) return 0;
-    const int nk = g.K / 64, tiles = cdiv(g.N, 64);
-    int splits = dec_splits_for(tiles, nk);
-    if (dec_splits_override() > 0) splits = std::min(dec_splits_override(), nk);
-    const int kc = cdiv(nk, splits) * 64;
-    splits = cdiv(g.K, kc);
-    if ((long)splits * g.M * g.N > g.splitk_ws_elems) return 0;
-    if (g.w8_scale) launch_dec<T, EPI_STORE, true, true>(g, tiles, splits, kc, st);
-    else launch_dec<T, EPI_STORE, true, false>(g, tiles, splits, kc, st);
-    return splits;
+    const DecPlan p = dec_plan(g.N, g.K, g.M, g.splitk_ws_elems);
+    if (p.splits) launch_dec<T, EPI_STORE, true>(g, cdiv(g.N, 64), p.splits, p.kc, st);
+    return p.splits;
 }
-
 
 int launch_gemm_partials(DType dt, const GemmArgs& g, hipStream_t st) {
     return dt == DType::F16 ? launch_partials_t<half_t>(g, st) : launch_partials_t<bf16_t>(g, st);

@@ -1,5 +1,5 @@
 """GPU A/B of encoder GEMM variants (gemm.hip gemm8p_kernel; DV_VARIANTS = whisper_mi355x_set_gemm_variant values,
-e.g. -1 auto, 14 the transposed-accumulator epilogue): the large-v3 encoder shapes (32 windows x 1500 rows, random
+-1 auto, 0 register-staged, 1 the 128x128 LDS-DMA kernel, >= 2 gemm8p wherever the shape is big): the large-v3 encoder shapes (32 windows x 1500 rows, random
 bf16 operands, the engine's epilogues incl. bias), each variant timed over 5 launches in rounds so that clock drift
 spreads over all of them; outputs must be bitwise equal across variants."""
 import os
