@@ -791,9 +791,7 @@ int encode_windows(Context* c, whisper_state* s, const int* jobs, const int* see
 
 // ---- decoder --------------------------------------------------------------------------------------
 // n_tok tokens (ragged over slots) -> logits of n_rows rows (row r = token lrows[r]) into w.logits.
-// Token metadata must already be in w.h_ints: [tok | pos | slot | - | - ] with stride cap_tok and
-// lrows at 5*cap_tok.
-// token metadata (already in w.h_ints: [tok | pos | slot | - | -], lrows at 5*cap_tok) -> device
+// token metadata (already in w.h_ints: [tok | pos | slot | - | -] with stride cap_tok, lrows at 5*cap_tok) -> device
 static void decoder_upload(Context* c, whisper_state* s, int n_tok, int n_rows, bool tiles) {
     const Hparams& hp = c->hp;
     Workspace& w = s->ws;
@@ -862,6 +860,12 @@ static int pdec_max() {
     return e ? std::max(0, std::min(kPdecMaxRows, atoi(e))) : kPdecMaxRows;
 }
 
+// Rows up to which a decode step's row group takes the small-M path, by the two switches above
+static int small_rows_max(Context* c) { return c->quant ? std::max(quant_small_max(), small_m_max()) : small_m_max(); }
+
+// fp8 mode: decode steps read the e4m3 copies of the decoder's projection weights (split-K path only)
+static bool dec_fp8(Context* c) { return c->fp8_enc && !c->dec8.empty(); }
+
 // The per-call switches that choose a decode step's kernels, folded into the key of its captured graph.
 static int dec_path_sig() {
     return small_m_max() | (std::min(std::max(quant_small_max(), 0), 1023) << 6) |
@@ -880,8 +884,8 @@ static bool pdec_blocks(Context* c) {
 // weights are f16 / bf16 or GGML blocks (not the fp8 decoder copies), the device has the 256 CUs the
 // grid is built for, and the step is in the cross K/V cache form.
 static bool pdec_use(Context* c, whisper_state* s, int n, bool xdirect) {
-    if (xdirect || s->pdec_block || s->pdec_off || n < 1 || n > pdec_max()) return false;
-    if (c->fp8_enc && !c->dec8.empty()) return false;
+    if (xdirect || s->pdec_off || n < 1 || n > pdec_max()) return false;
+    if (dec_fp8(c)) return false;
     // one weight form for every decoder matrix (the kernel is built per form)
     const bool quant = c->w.dec[0].qqkv.type != 0;
     for (const LayerW& L : c->w.dec)
@@ -897,6 +901,49 @@ static bool pdec_use(Context* c, whisper_state* s, int n, bool xdirect) {
         return v;
     }();
     return cus == 256;
+}
+
+// Row groups of a decode step. The split-K pass (every LayerNorm folded into a split-K reduce) takes at
+// most 128 rows, so a step over n > 128 clips runs as ceil(n / 128) groups of near-equal size,
+// alternating between the state's two streams (forked from and joined back into the state's stream:
+// branches of the step's hipGraph); two groups for 129..256 clips measured the same as the unfused
+// path in bf16 (turbo at 256 clips: decode 213 vs 217 ms per step) and the fp8 decoder weights exist
+// only on the split-K path.
+// Splitting steps of 32..128 clips into two concurrent groups measured slower on large-v3 at 128 clips
+// (2360-2392 vs 2729-2740 audio-s/s: the cross-attention pass at 64 clips per group reads E at 3.6
+// instead of 4.7 TB/s), and so did two separate graphs on two streams (942 vs 843 ms of decode per
+// step, profiles/r02_dec_groups_ab.txt); both were removed.
+static int dec_groups(int n_tok) { return cdiv(n_tok, 128); }
+
+// How a decode step of n clips (one token per clip, logits of every row) runs, decided here and nowhere
+// else: decoder_launch and the row functions take the plan and follow it, dec_graph keys the step's graph
+// on its path. A row group runs as the persistent launch (decoder_rows_pdec; <= 4 clips, so one group),
+// the small-M GEMMs (decoder_rows_small) or the split-K pass (decoder_rows_step); the small-M condition is
+// evaluated on a group's rows, so the last, shorter group of a step may take another path than the others.
+enum StepPath { STEP_PDEC, STEP_SMALL, STEP_SPLITK };
+struct StepPlan {
+    int n;               // clips (rows) of the step
+    int groups, gsz;     // row groups and the rows of each but the last (n - (groups - 1) * gsz rows)
+    StepPath path, tail_path;  // of a group of gsz rows, of the last group
+    bool xdirect;        // cross attention from the encoder output (else from the cross K/V cache)
+    bool w8;             // the split-K pass reads the fp8 weights
+    bool pdec_ok;        // false: a re-run of a step whose persistent launch gave up
+    bool pipe;           // built into a pipelined step graph (its advance kernel copies the error word)
+};
+static StepPlan step_plan(Context* c, whisper_state* s, int n, bool xdirect, bool pdec_ok = true) {
+    StepPlan P{};
+    P.n = n; P.groups = dec_groups(n); P.gsz = cdiv(n, P.groups);
+    P.xdirect = xdirect; P.w8 = dec_fp8(c); P.pdec_ok = pdec_ok;
+    const int d = c->hp.n_text_state;
+    const bool pd = pdec_ok && pdec_use(c, s, n, xdirect);
+    auto path = [&](int rows) {
+        if (pd) return STEP_PDEC;
+        const bool small = !P.w8 && rows <= small_rows_max(c) && gemm_small_ok(rows, d, true) && gemm_small_ok(rows, 4 * d, false);
+        return small ? STEP_SMALL : STEP_SPLITK;
+    };
+    P.path = path(P.gsz);
+    P.tail_path = P.groups == 1 ? P.path : path(n - (P.groups - 1) * P.gsz);
+    return P;
 }
 
 // Device array of the decoder layers' pointers (once per context and weight form): the arena's
@@ -939,7 +986,7 @@ static void pdec_prepare(Context* c, whisper_state* s) {
 // One decode step of the view's rows as the persistent launch + the logits GEMM (graph-capturable).
 // The launch's error word is copied to the host (a node of the step's graph): decode_step checks it
 // after the step's synchronisation and re-runs the step on the per-kernel path if the launch gave up.
-static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v) {
+static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v, bool pipe) {
     const Hparams& hp = c->hp;
     Workspace& w = s->ws;
     const int d = hp.n_text_state, H = hp.n_text_head, L = hp.n_text_layer, V = hp.n_vocab;
@@ -972,11 +1019,66 @@ static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v) {
         launch_pdec(c->dt, a, st);
     }
     // (a pipelined step graph's advance kernel writes the error word to its ring slot instead)
-    if (!s->pipe_capture)
+    if (!pipe)
         WM_CHECK(hipMemcpyAsync(w.h_pd_err, (const char*)w.pd_sync + a.gr.err_bytes, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     GemmArgs g = gemm_plain(a.out_dh, n, d, c->w.tok_emb, V, nullptr, w.logits + (size_t)v.r0 * V, V);
     tgemm_ws(s, K_GEMM_DEC, c->dt, EPI_F32, g, st, v.splitk, v.splitk_elems);
 }
+
+// The view's rows of the token arrays and activations (what the three layer-by-layer passes below work on)
+struct DecRows {
+    int n;
+    hipStream_t st;
+    int *tok, *pos, *slot, *nkv_self, *nkv_cross;
+    float* dx;
+    void *dh, *dq, *datt, *dff, *qx;
+};
+static DecRows dec_rows(Context* c, whisper_state* s, const DecView& v) {
+    Workspace& w = s->ws;
+    const size_t d = c->hp.n_text_state, H = c->hp.n_text_head, E = esize(c->dt), r0 = v.r0;
+    return DecRows{v.n, v.st, w.tok + r0, w.pos + r0, w.slot + r0, w.nkv_self + r0, w.nkv_cross + r0, w.dx + r0 * d,
+                   (char*)w.dh + r0 * d * E, (char*)w.dq + r0 * d * E, (char*)w.datt + r0 * d * E, (char*)w.dff + r0 * 4 * d * E,
+                   w.qx ? (void*)((char*)w.qx + r0 * 2 * H * d * E) : nullptr};
+}
+
+// Token + positional embedding of the rows into dx; `ln`: and layer 0's first LayerNorm of it into dh (one launch)
+static void embed_rows(Context* c, const DecRows& r, bool ln) {
+    const Weights& W = c->w;
+    const int d = c->hp.n_text_state;
+    const void* te = W.tok_emb_f32 ? (const void*)W.tok_emb_f32 : W.tok_emb;
+    if (ln) launch_embed_ln(c->dt, te, W.tok_emb_f32 != nullptr, W.pos_d, r.tok, r.pos, r.n, d, r.dx, W.dec[0].ln1_w, W.dec[0].ln1_b, r.dh, r.st);
+    else launch_embed(c->dt, te, W.tok_emb_f32 != nullptr, W.pos_d, r.tok, r.pos, r.n, d, r.dx, r.st);
+}
+
+// Layer l's cross attention from the encoder output (kernels/xattn.hip), after the caller's cross-Q GEMM
+// left q in dq: Q' = s Wk^T q (hi/lo) -> one pass over E per clip -> split merge + Wv into datt. (Fusing
+// the cross-Q reduce into the Q' projection was bit-identical but slower, 855 vs 848 ms per step at 128
+// clips: removed.) step_cls: the timing class of the pass over E; the roofline's K_ATTN_CROSS holds decode
+// steps only (E bytes read once per clip and layer), prefill counts it as K_OTHER.
+static void xattn_tail(Context* c, whisper_state* s, const DecView& v, const DecRows& r, int l, int step_cls, bool kt_layer) {
+    const Weights& W = c->w;
+    const DType dt = c->dt;
+    const int d = c->hp.n_text_state, H = c->hp.n_text_head, Ta = c->hp.n_audio_ctx, n = r.n;
+    const int S = xattn_splits(n, Ta);
+    hipStream_t st = r.st;
+    {
+        KT kt(s, K_GEMM_DEC, 2.0 * d * d + 2.0 * n * d + 4.0 * n * H * d, st);
+        launch_xattn_qproj(dt, r.dq, (const char*)W.wkT + (size_t)l * H * d * 64 * 2, n, d, H, c->k_scale, r.qx, st);
+    }
+    {
+        KT kt(s, step_cls, (double)n * Ta * d * 2, st, kt_layer);
+        launch_xattn_step(dt, s->ws.enc, r.slot, r.qx, n, Ta, d, S, kXattnThr, v.xo, v.xml, st);
+    }
+    {
+        KT kt(s, K_GEMM_DEC, 2.0 * d * d + 4.0 * n * S * d + 2.0 * n * d, st);
+        launch_xattn_combine(dt, v.xo, v.xml, S, (const char*)W.wkv_cross + (size_t)(2 * l + 1) * d * d * 2,
+                             W.bkv_cross + (size_t)(2 * l + 1) * d, n, d, H, r.datt, st);
+    }
+}
+
+// kernel timing (bench roofline): bits 16..23 of the mask = time the per-layer attention launches of
+// every k-th layer only (fewer event nodes in the timed decode graphs; every layer does the same work)
+static int kt_layer_stride(const whisper_state* s) { return std::max(1, (s->ktime_mask >> 16) & 0xFF); }
 
 // Decode step over <= 32 rows (the app's one clip per call, whisper.rs:83-85 / state.rs:147; one
 // rank's 16-clip shard of configs[3] at 8 GPUs), kernels only: every projection is ONE launch of
@@ -986,56 +1088,42 @@ static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v) {
 // -> cross attention -> Wxo (+x) -> FC1 (GELU) -> FC2 (+x): 8 launches in the cache form, against
 // 15 on the split-K path. Results per row do not depend on the other rows (batch == single within
 // this path); they differ in the last bits from the split-K path's (another summation order).
-static void decoder_rows_small(Context* c, whisper_state* s, const DecView& v, bool xdirect, double self_share,
-                               int kt_stride) {
+static void decoder_rows_small(Context* c, whisper_state* s, const DecView& v, bool xdirect, double self_share) {
     const Hparams& hp = c->hp;
     Workspace& w = s->ws;
     const int d = hp.n_text_state, H = hp.n_text_head, V = hp.n_vocab, L = hp.n_text_layer;
     const DType dt = c->dt;
     const Weights& W = c->w;
-    const size_t E = esize(dt);
     hipStream_t st = v.st;
     const int n = v.n;
-    int* tok = w.tok + v.r0;
-    int* pos = w.pos + v.r0;
-    int* slot = w.slot + v.r0;
-    int* nkv_cross = w.nkv_cross + v.r0;
-    float* dx = w.dx + (size_t)v.r0 * d;
-    void* dh = (char*)w.dh + (size_t)v.r0 * d * E;
-    void* dq = (char*)w.dq + (size_t)v.r0 * d * E;
-    void* datt = (char*)w.datt + (size_t)v.r0 * d * E;
-    void* dff = (char*)w.dff + (size_t)v.r0 * 4 * d * E;
-    void* qx = w.qx ? (void*)((char*)w.qx + (size_t)v.r0 * 2 * H * d * E) : nullptr;
+    const DecRows r = dec_rows(c, s, v);
+    const int kt_stride = kt_layer_stride(s);
     float* raw = v.splitk;  // f32 projection sums handed to the attention prologues ([n][3d] / [n][d])
     const double kvrow = (double)H * 64 * 2 * 2;
-    const QMat* qm = nullptr;  // the layer's block-quantized matrix of the next `small` call (quantized files)
-    auto small = [&](int epi, const void* A, int K, const void* Wt, int N, const float* bias, void* out, long ldo,
-                     const float* lnw = nullptr, const float* lnb = nullptr) {
+    // q: the matrix's GGML blocks (quantized files; type 0: none, the dense Wt is read)
+    auto small = [&](const QMat& q, int epi, const void* A, int K, const void* Wt, int N, const float* bias, void* out,
+                     long ldo, const float* lnw = nullptr, const float* lnb = nullptr) {
         GemmArgs g = gemm_plain(A, n, K, Wt, N, bias, out, ldo);
         g.a_ln_w = lnw;
         g.a_ln_b = lnb;
-        if (qm) g.q = *qm;
-        qm = nullptr;
+        g.q = q;
         KT kt(s, K_GEMM_DEC, 2.0 * N * K + 2.0 * n * K + 4.0 * n * N, st);
         launch_gemm_small(dt, epi, g, lnw != nullptr, st);
     };
-    launch_embed(dt, W.tok_emb_f32 ? (const void*)W.tok_emb_f32 : W.tok_emb, W.tok_emb_f32 != nullptr, W.pos_d, tok, pos, n, d,
-                 dx, st);
+    embed_rows(c, r, false);
     for (int l = 0; l < L; l++) {
         const LayerW& Lw = W.dec[l];
         const bool kt_layer = l % kt_stride == 0;
         // self attention: LN1 in the QKV GEMM, raw sums to the attention prologue (+ bias, q/k scale)
-        qm = &Lw.qqkv;
-        small(EPI_F32, dx, d, Lw.wqkv, 3 * d, nullptr, raw, 3 * d, Lw.ln1_w, Lw.ln1_b);
+        small(Lw.qqkv, EPI_F32, r.dx, d, Lw.wqkv, 3 * d, nullptr, raw, 3 * d, Lw.ln1_w, Lw.ln1_b);
         {
             const DecSlabs sl{raw, 1, (long)n * 3 * d, 3 * d, Lw.bqkv, c->k_scale};
             KT kt(s, K_ATTN_SELF, self_share, st, kt_layer);
-            launch_attn_self_step(dt, sl, w.self, slot, pos, n, L, l, H, hp.n_text_ctx, d, datt, st);
+            launch_attn_self_step(dt, sl, w.self, r.slot, r.pos, n, L, l, H, hp.n_text_ctx, d, r.datt, st);
         }
-        qm = &Lw.qo;
-        small(EPI_RESID, datt, d, Lw.wo, d, Lw.bo, dx, d);
+        small(Lw.qo, EPI_RESID, r.datt, d, Lw.wo, d, Lw.bo, r.dx, d);
         if (xdirect) {
-            GemmArgs g = gemm_plain(dx, n, d, Lw.wxq, d, Lw.bxq, dq, d);
+            GemmArgs g = gemm_plain(r.dx, n, d, Lw.wxq, d, Lw.bxq, r.dq, d);
             g.scale = c->k_scale; g.sc_div = d; g.sc_mod = 1; g.sc_lim = 1;
             g.a_ln_w = Lw.lnx_w; g.a_ln_b = Lw.lnx_b;
             g.q = Lw.qxq;
@@ -1043,213 +1131,176 @@ static void decoder_rows_small(Context* c, whisper_state* s, const DecView& v, b
                 KT kt(s, K_GEMM_DEC, 2.0 * d * d + 2.0 * n * d + 4.0 * n * d, st);
                 launch_gemm_small(dt, EPI_STORE, g, true, st);
             }
-            const int Ta = hp.n_audio_ctx, S = xattn_splits(n, Ta);
-            {
-                KT kt(s, K_GEMM_DEC, 2.0 * d * d + 2.0 * n * d + 4.0 * n * H * d, st);
-                launch_xattn_qproj(dt, dq, (const char*)W.wkT + (size_t)l * H * d * 64 * 2, n, d, H, c->k_scale, qx, st);
-            }
-            {
-                KT kt(s, K_ATTN_CROSS, (double)n * Ta * d * 2, st, kt_layer);
-                launch_xattn_step(dt, w.enc, slot, qx, n, Ta, d, S, kXattnThr, v.xo, v.xml, st);
-            }
-            {
-                KT kt(s, K_GEMM_DEC, 2.0 * d * d + 4.0 * n * S * d + 2.0 * n * d, st);
-                launch_xattn_combine(dt, v.xo, v.xml, S, (const char*)W.wkv_cross + (size_t)(2 * l + 1) * d * d * 2,
-                                     W.bkv_cross + (size_t)(2 * l + 1) * d, n, d, H, datt, st);
-            }
+            xattn_tail(c, s, v, r, l, K_ATTN_CROSS, kt_layer);
         } else {
-            qm = &Lw.qxq;
-            small(EPI_F32, dx, d, Lw.wxq, d, nullptr, raw, d, Lw.lnx_w, Lw.lnx_b);
+            small(Lw.qxq, EPI_F32, r.dx, d, Lw.wxq, d, nullptr, raw, d, Lw.lnx_w, Lw.lnx_b);
             const DecSlabs sl{raw, 1, (long)n * d, d, Lw.bxq, c->k_scale};
             KT kt(s, K_ATTN_CROSS, (double)n * hp.n_audio_ctx * kvrow, st, kt_layer);
-            launch_attn_cross_step(dt, sl, w.cross, slot, nkv_cross, n, L, l, H, hp.n_audio_ctx, d, datt, st);
+            launch_attn_cross_step(dt, sl, w.cross, r.slot, r.nkv_cross, n, L, l, H, hp.n_audio_ctx, d, r.datt, st);
         }
-        qm = &Lw.qxo;
-        small(EPI_RESID, datt, d, Lw.wxo, d, Lw.bxo, dx, d);
-        qm = &Lw.q1;
-        small(EPI_GELU, dx, d, Lw.w1, 4 * d, Lw.b1, dff, 4 * d, Lw.ln2_w, Lw.ln2_b);
-        qm = &Lw.q2;
-        small(EPI_RESID, dff, 4 * d, Lw.w2, d, Lw.b2, dx, d);
+        small(Lw.qxo, EPI_RESID, r.datt, d, Lw.wxo, d, Lw.bxo, r.dx, d);
+        small(Lw.q1, EPI_GELU, r.dx, d, Lw.w1, 4 * d, Lw.b1, r.dff, 4 * d, Lw.ln2_w, Lw.ln2_b);
+        small(Lw.q2, EPI_RESID, r.dff, 4 * d, Lw.w2, d, Lw.b2, r.dx, d);
     }
-    launch_layernorm(dt, dx, nullptr, n, d, W.lnd_w, W.lnd_b, dh, st);
-    GemmArgs g = gemm_plain(dh, n, d, W.tok_emb, V, nullptr, w.logits + (size_t)v.r0 * V, V);
+    launch_layernorm(dt, r.dx, nullptr, n, d, W.lnd_w, W.lnd_b, r.dh, st);
+    GemmArgs g = gemm_plain(r.dh, n, d, W.tok_emb, V, nullptr, w.logits + (size_t)v.r0 * V, V);
     tgemm_ws(s, K_GEMM_DEC, dt, EPI_F32, g, st, v.splitk, v.splitk_elems);
 }
 
-// The decoder forward over the view's tokens + logits; kernels only (graph-capturable). `fused`
-// (decode steps: one token per clip, logits for every row, <= 128 rows per view): every LayerNorm
-// is folded into the embedding or into the split-K reduce of the preceding residual GEMM.
-// Otherwise (prefill, one view at r0 = 0) logits of n_rows rows (row r = token lrows[r]).
-// `al` (the token-timestamp alignment, align_windows): the unfused cache-form pass; after the cross-Q GEMM of a
-// layer that has alignment heads the score kernel runs on those rows, and the pass ends after the cross-Q of
-// the highest such layer (the remaining layers, the final LN and the logits GEMM are not needed).
-struct AlignPass {
-    const AlignClip* clips;
-    int n_clips, max_rows;
-    long total_rows;
-    float* P;
-};
-static void decoder_rows(Context* c, whisper_state* s, const DecView& v, int n_rows, bool fused, bool xdirect,
-                         double self_share, const AlignPass* al = nullptr) {
+// The dense weights of decoder layer l for the two split-K / unfused passes below; a block-quantized file's
+// blocks are dequantized into the scratch first (one launch)
+static LayerW layer_dense(Context* c, whisper_state* s, int l, hipStream_t st) {
+    LayerW Lw = c->w.dec[l];
+    if (c->quant) {
+        const LayerMats m = layer_mats(c, s, true, l, st);
+        Lw.wqkv = (void*)m.wqkv; Lw.wo = (void*)m.wo; Lw.wxq = (void*)m.wxq; Lw.wxo = (void*)m.wxo;
+        Lw.w1 = (void*)m.w1; Lw.w2 = (void*)m.w2;
+    }
+    return Lw;
+}
+
+// One decode step of the view's rows on the split-K path (one token per clip, logits of every row, <= 128
+// rows per view); kernels only (graph-capturable). Every LayerNorm is folded into the embedding or into the
+// split-K reduce of the preceding residual GEMM, and the QKV (and, cache form, cross-Q) projections leave
+// split-K partial sums that the attention kernels reduce in their prologue (no separate reduce launch).
+// P.w8 (fp8 mode): the projections read the e4m3 copies of the layer's weights.
+static void decoder_rows_step(Context* c, whisper_state* s, const DecView& v, const StepPlan& P, double self_share) {
     const Hparams& hp = c->hp;
     Workspace& w = s->ws;
     const int d = hp.n_text_state, H = hp.n_text_head, V = hp.n_vocab, L = hp.n_text_layer;
     const DType dt = c->dt;
     const Weights& W = c->w;
-    const size_t E = esize(dt);
     hipStream_t st = v.st;
-    const int n_tok = v.n;
+    const int n = v.n;
+    const DecRows r = dec_rows(c, s, v);
     const int KCLS = K_GEMM_DEC;
     const double kvrow = (double)H * 64 * 2 * 2;  // K and V row bytes of one position, all heads
-    int* tok = w.tok + v.r0;
-    int* pos = w.pos + v.r0;
-    int* slot = w.slot + v.r0;
-    int* nkv_self = w.nkv_self + v.r0;
-    int* nkv_cross = w.nkv_cross + v.r0;
-    float* dx = w.dx + (size_t)v.r0 * d;
-    void* dh = (char*)w.dh + (size_t)v.r0 * d * E;
-    void* dq = (char*)w.dq + (size_t)v.r0 * d * E;
-    void* datt = (char*)w.datt + (size_t)v.r0 * d * E;
-    void* dff = (char*)w.dff + (size_t)v.r0 * 4 * d * E;
-    void* qx = w.qx ? (void*)((char*)w.qx + (size_t)v.r0 * 2 * H * d * E) : nullptr;
-    auto gemm = [&](int cls, int epi, const GemmArgs& g) { tgemm_ws(s, cls, dt, epi, g, st, v.splitk, v.splitk_elems); };
-    // fp8 mode: decode steps read the e4m3 copies of the layer's projection weights
-    const bool w8 = fused && c->fp8_enc && !c->dec8.empty();
+    const int kt_stride = kt_layer_stride(s);
+    auto gemm = [&](int epi, const GemmArgs& g) { tgemm_ws(s, KCLS, dt, epi, g, st, v.splitk, v.splitk_elems); };
     auto use8 = [&](GemmArgs g, void* q8, float* sc) {
-        if (w8) { g.B = q8; g.w8_scale = sc; }
+        if (P.w8) { g.B = q8; g.w8_scale = sc; }
         return g;
     };
-    auto resid = [&](const void* A, int K, const void* Wt, const float* bias, const float* lnw, const float* lnb,
-                     void* q8 = nullptr, float* sc = nullptr) {
-        GemmArgs g = use8(gemm_plain(A, n_tok, K, Wt, d, bias, dx, d), q8, sc);
-        if (fused) { g.ln_w = lnw; g.ln_b = lnb; g.ln_out = dh; }
-        gemm(KCLS, EPI_RESID, g);
-        if (!fused && lnw) launch_layernorm(dt, dx, nullptr, n_tok, d, lnw, lnb, dh, st);
+    // x += A W + bias; its reduce also writes LayerNorm(x; lnw, lnb) into dh
+    auto resid = [&](const void* A, int K, const void* Wt, const float* bias, const float* lnw, const float* lnb, void* q8,
+                     float* sc) {
+        GemmArgs g = use8(gemm_plain(A, n, K, Wt, d, bias, r.dx, d), q8, sc);
+        g.ln_w = lnw; g.ln_b = lnb; g.ln_out = r.dh;
+        gemm(EPI_RESID, g);
     };
-    // kernel timing (bench roofline): bits 8..15 of the mask = time the per-layer attention launches of
-    // every k-th layer only (fewer event nodes in the timed decode graphs; every layer does the same work)
-    const int kt_stride = std::max(1, (s->ktime_mask >> 16) & 0xFF);
-    if (fused && pdec_use(c, s, n_tok, xdirect)) {
-        decoder_rows_pdec(c, s, v);
-        return;
-    }
-    // (the persistent and small-M paths embed the tokens themselves)
-    if (fused && !w8 && ((c->quant && n_tok <= quant_small_max()) || n_tok <= small_m_max()) && gemm_small_ok(n_tok, d, true) &&
-        gemm_small_ok(n_tok, 4 * d, false)) {
-        decoder_rows_small(c, s, v, xdirect, self_share, kt_stride);
-        return;
-    }
-    if (fused) launch_embed_ln(dt, W.tok_emb_f32 ? (const void*)W.tok_emb_f32 : W.tok_emb, W.tok_emb_f32 != nullptr, W.pos_d, tok, pos, n_tok, d, dx, W.dec[0].ln1_w, W.dec[0].ln1_b, dh, st);
-    else {
-        launch_embed(dt, W.tok_emb_f32 ? (const void*)W.tok_emb_f32 : W.tok_emb, W.tok_emb_f32 != nullptr, W.pos_d, tok, pos, n_tok, d, dx, st);
-        launch_layernorm(dt, dx, nullptr, n_tok, d, W.dec[0].ln1_w, W.dec[0].ln1_b, dh, st);
-    }
-    // decode steps: the QKV (and, cache mode, cross-Q) projections leave split-K partial sums that
-    // the attention kernels reduce in their prologue (no separate reduce launch)
     auto partials = [&](const void* A, const void* Wt, int N, const float* bias, float scale, void* q8,
                         float* sc) -> DecSlabs {
-        GemmArgs g = use8(gemm_plain(A, n_tok, d, Wt, N, bias, nullptr, N), q8, sc);
+        GemmArgs g = use8(gemm_plain(A, n, d, Wt, N, bias, nullptr, N), q8, sc);
         g.splitk_ws = v.splitk;
         g.splitk_ws_elems = v.splitk_elems;
         g.slab_wt = 1;
         KT kt(s, KCLS, 2.0 * g.N * g.K + 2.0 * g.M * g.K + 4.0 * g.M * g.N, st);
         const int splits = launch_gemm_partials(dt, g, st);
         if (splits <= 0 || splits > 16) WM_FAIL("decode partials GEMM not applicable (splits %d)", splits);
-        return DecSlabs{v.splitk, splits, (long)n_tok * N, N, bias, scale};
+        return DecSlabs{v.splitk, splits, (long)n * N, N, bias, scale};
     };
+    embed_rows(c, r, true);
     for (int l = 0; l < L; l++) {
-        const int lw = l;
-        LayerW Lw = W.dec[lw];
-        if (c->quant) {  // prefill / language detection: this layer's blocks dequantized into the scratch
-            const LayerMats m = layer_mats(c, s, true, lw, st);
-            Lw.wqkv = (void*)m.wqkv; Lw.wo = (void*)m.wo; Lw.wxq = (void*)m.wxq; Lw.wxo = (void*)m.wxo;
-            Lw.w1 = (void*)m.w1; Lw.w2 = (void*)m.w2;
-        }
+        const LayerW Lw = layer_dense(c, s, l, st);
         static const Context::Fp8Dec no8{};
-        const Context::Fp8Dec& F = w8 ? c->dec8[l] : no8;
+        const Context::Fp8Dec& F = P.w8 ? c->dec8[l] : no8;
         const bool kt_layer = l % kt_stride == 0;
-        if (fused) {
-            const DecSlabs sl = partials(dh, Lw.wqkv, 3 * d, Lw.bqkv, c->k_scale, F.wqkv, F.sqkv);
+        {
+            const DecSlabs sl = partials(r.dh, Lw.wqkv, 3 * d, Lw.bqkv, c->k_scale, F.wqkv, F.sqkv);
             KT kt(s, K_ATTN_SELF, self_share, st, kt_layer);
-            launch_attn_self_step(dt, sl, w.self, slot, pos, n_tok, L, l, H, hp.n_text_ctx, d, datt, st);
-        } else {
-            GemmArgs g = gemm_plain(dh, n_tok, d, Lw.wqkv, 3 * d, Lw.bqkv, dq, d);
-            g.scale = c->k_scale;
-            g.cache = w.self; g.row_slot = slot; g.row_pos = pos; g.L = L; g.layer = l; g.H = H;
-            g.ctx = hp.n_text_ctx; g.d = d;
-            gemm(KCLS, EPI_QKV_DEC, g);
-            KT kt(s, K_ATTN_SELF, self_share, st, kt_layer);
-            launch_attn_prefill(dt, dq, d, w.self, slot, nkv_self, w.qtiles, w.n_qtiles, L, l, H, hp.n_text_ctx, d, datt, st);
+            launch_attn_self_step(dt, sl, w.self, r.slot, r.pos, n, L, l, H, hp.n_text_ctx, d, r.datt, st);
         }
-        resid(datt, d, Lw.wo, Lw.bo, Lw.lnx_w, Lw.lnx_b, F.wo, F.so);
-        if (xdirect) {
-            // cross attention from the encoder output (kernels/xattn.hip): q -> Q' = s Wk^T q (hi/lo)
-            // -> one pass over E per clip -> split merge + Wv. (Fusing the cross-Q reduce into the Q'
-            // projection was bit-identical but slower, 855 vs 848 ms per step at 128 clips: removed.)
-            const void* wkt_l = (const char*)W.wkT + (size_t)lw * H * d * 64 * 2;
-            {
-                GemmArgs g = use8(gemm_plain(dh, n_tok, d, Lw.wxq, d, Lw.bxq, dq, d), F.wxq, F.sxq);
-                g.scale = c->k_scale; g.sc_div = d; g.sc_mod = 1; g.sc_lim = 1;
-                gemm(KCLS, EPI_STORE, g);
-                KT kt(s, KCLS, 2.0 * d * d + 2.0 * n_tok * d + 4.0 * n_tok * H * d, st);
-                launch_xattn_qproj(dt, dq, wkt_l, n_tok, d, H, c->k_scale, qx, st);
-            }
-            const int Ta = hp.n_audio_ctx, S = xattn_splits(n_tok, Ta);
-            {
-                // the roofline class holds decode steps only (E bytes read once per clip and layer)
-                KT kt(s, fused ? K_ATTN_CROSS : K_OTHER, (double)n_tok * Ta * d * 2, st, kt_layer);
-                launch_xattn_step(dt, w.enc, slot, qx, n_tok, Ta, d, S, kXattnThr, v.xo, v.xml, st);
-            }
-            {
-                KT kt(s, KCLS, 2.0 * d * d + 4.0 * n_tok * S * d + 2.0 * n_tok * d, st);
-                launch_xattn_combine(dt, v.xo, v.xml, S, (const char*)W.wkv_cross + (size_t)(2 * lw + 1) * d * d * 2,
-                                     W.bkv_cross + (size_t)(2 * lw + 1) * d, n_tok, d, H, datt, st);
-            }
-        } else if (fused) {
-            const DecSlabs sl = partials(dh, Lw.wxq, d, Lw.bxq, c->k_scale, F.wxq, F.sxq);
-            KT kt(s, K_ATTN_CROSS, (double)n_tok * hp.n_audio_ctx * kvrow, st, kt_layer);  // decode steps only
-            launch_attn_cross_step(dt, sl, w.cross, slot, nkv_cross, n_tok, L, l, H, hp.n_audio_ctx, d, datt, st);
-        } else {
-            GemmArgs g = gemm_plain(dh, n_tok, d, Lw.wxq, d, Lw.bxq, dq, d);
+        resid(r.datt, d, Lw.wo, Lw.bo, Lw.lnx_w, Lw.lnx_b, F.wo, F.so);
+        if (P.xdirect) {
+            GemmArgs g = use8(gemm_plain(r.dh, n, d, Lw.wxq, d, Lw.bxq, r.dq, d), F.wxq, F.sxq);
             g.scale = c->k_scale; g.sc_div = d; g.sc_mod = 1; g.sc_lim = 1;
-            gemm(KCLS, EPI_STORE, g);
+            gemm(EPI_STORE, g);
+            xattn_tail(c, s, v, r, l, K_ATTN_CROSS, kt_layer);
+        } else {
+            const DecSlabs sl = partials(r.dh, Lw.wxq, d, Lw.bxq, c->k_scale, F.wxq, F.sxq);
+            KT kt(s, K_ATTN_CROSS, (double)n * hp.n_audio_ctx * kvrow, st, kt_layer);
+            launch_attn_cross_step(dt, sl, w.cross, r.slot, r.nkv_cross, n, L, l, H, hp.n_audio_ctx, d, r.datt, st);
+        }
+        resid(r.datt, d, Lw.wxo, Lw.bxo, Lw.ln2_w, Lw.ln2_b, F.wxo, F.sxo);
+        gemm(EPI_GELU, use8(gemm_plain(r.dh, n, d, Lw.w1, 4 * d, Lw.b1, r.dff, 4 * d), F.w1, F.s1));
+        if (l + 1 < L) resid(r.dff, 4 * d, Lw.w2, Lw.b2, W.dec[l + 1].ln1_w, W.dec[l + 1].ln1_b, F.w2, F.s2);
+        else resid(r.dff, 4 * d, Lw.w2, Lw.b2, W.lnd_w, W.lnd_b, F.w2, F.s2);  // dh = final LN of every row
+    }
+    gemm(EPI_F32, gemm_plain(r.dh, n, d, W.tok_emb, V, nullptr, w.logits + (size_t)v.r0 * V, V));
+}
+
+// The unfused decoder forward over the view's tokens (prefill, language detection, whisper_decode: one view
+// at r0 = 0, over the attention tiles that decoder_upload built) + logits of n_rows rows (row r = token
+// lrows[r]); kernels only.
+// `al` (the token-timestamp alignment, align_windows; cache form): after the cross-Q GEMM of a layer that has
+// alignment heads the score kernel runs on those rows, and the pass ends after the cross-Q of the highest
+// such layer (the remaining layers, the final LN and the logits GEMM are not needed).
+struct AlignPass {
+    const AlignClip* clips;
+    int n_clips, max_rows;
+    long total_rows;
+    float* P;
+};
+static void decoder_rows_prefill(Context* c, whisper_state* s, const DecView& v, int n_rows, bool xdirect,
+                                 const AlignPass* al = nullptr) {
+    const Hparams& hp = c->hp;
+    Workspace& w = s->ws;
+    const int d = hp.n_text_state, H = hp.n_text_head, V = hp.n_vocab, L = hp.n_text_layer;
+    const DType dt = c->dt;
+    const Weights& W = c->w;
+    hipStream_t st = v.st;
+    const int n = v.n;
+    const DecRows r = dec_rows(c, s, v);
+    const int KCLS = K_GEMM_DEC;
+    const double kvrow = (double)H * 64 * 2 * 2;  // K and V row bytes of one position, all heads
+    const int kt_stride = kt_layer_stride(s);
+    auto gemm = [&](int epi, const GemmArgs& g) { tgemm_ws(s, KCLS, dt, epi, g, st, v.splitk, v.splitk_elems); };
+    // x += A W + bias; then LayerNorm(x; lnw, lnb) into dh (lnw null: none)
+    auto resid = [&](const void* A, int K, const void* Wt, const float* bias, const float* lnw, const float* lnb) {
+        gemm(EPI_RESID, gemm_plain(A, n, K, Wt, d, bias, r.dx, d));
+        if (lnw) launch_layernorm(dt, r.dx, nullptr, n, d, lnw, lnb, r.dh, st);
+    };
+    embed_rows(c, r, false);
+    launch_layernorm(dt, r.dx, nullptr, n, d, W.dec[0].ln1_w, W.dec[0].ln1_b, r.dh, st);
+    for (int l = 0; l < L; l++) {
+        const LayerW Lw = layer_dense(c, s, l, st);
+        const bool kt_layer = l % kt_stride == 0;
+        {
+            GemmArgs g = gemm_plain(r.dh, n, d, Lw.wqkv, 3 * d, Lw.bqkv, r.dq, d);
+            g.scale = c->k_scale;
+            g.cache = w.self; g.row_slot = r.slot; g.row_pos = r.pos; g.L = L; g.layer = l; g.H = H;
+            g.ctx = hp.n_text_ctx; g.d = d;
+            gemm(EPI_QKV_DEC, g);
+            KT kt(s, K_ATTN_SELF, 1.0, st, kt_layer);
+            launch_attn_prefill(dt, r.dq, d, w.self, r.slot, r.nkv_self, w.qtiles, w.n_qtiles, L, l, H, hp.n_text_ctx, d, r.datt, st);
+        }
+        resid(r.datt, d, Lw.wo, Lw.bo, Lw.lnx_w, Lw.lnx_b);
+        GemmArgs gq = gemm_plain(r.dh, n, d, Lw.wxq, d, Lw.bxq, r.dq, d);
+        gq.scale = c->k_scale; gq.sc_div = d; gq.sc_mod = 1; gq.sc_lim = 1;
+        gemm(EPI_STORE, gq);
+        if (xdirect) {
+            xattn_tail(c, s, v, r, l, K_OTHER, kt_layer);
+        } else {
             if (al) {
                 const int k0 = c->dtw_layer_first[l], k1 = c->dtw_layer_first[l + 1];
                 if (k1 > k0) {
                     KT kt(s, K_ALIGN_SCORES, 2.0 * al->total_rows * hp.n_audio_ctx * 64 * (k1 - k0), st);
-                    launch_align_scores(dt, dq, d, w.cross, al->clips, al->n_clips, al->max_rows, L, l, H, hp.n_audio_ctx,
+                    launch_align_scores(dt, r.dq, d, w.cross, al->clips, al->n_clips, al->max_rows, L, l, H, hp.n_audio_ctx,
                                         (const int2*)c->dtw_heads_dev + k0, k1 - k0, al->P, st);
                 }
                 if (l == c->dtw_last_layer) return;
             }
-            KT kt(s, K_OTHER, (double)n_tok * hp.n_audio_ctx * kvrow, st);
-            launch_attn_prefill(dt, dq, d, w.cross, slot, nkv_cross, w.qtiles, w.n_qtiles, L, l, H, hp.n_audio_ctx, d, datt, st);
+            KT kt(s, K_OTHER, (double)n * hp.n_audio_ctx * kvrow, st);
+            launch_attn_prefill(dt, r.dq, d, w.cross, r.slot, r.nkv_cross, w.qtiles, w.n_qtiles, L, l, H, hp.n_audio_ctx, d, r.datt, st);
         }
-        resid(datt, d, Lw.wxo, Lw.bxo, Lw.ln2_w, Lw.ln2_b, F.wxo, F.sxo);
-        gemm(KCLS, EPI_GELU, use8(gemm_plain(dh, n_tok, d, Lw.w1, 4 * d, Lw.b1, dff, 4 * d), F.w1, F.s1));
-        if (l + 1 < L) resid(dff, 4 * d, Lw.w2, Lw.b2, W.dec[l + 1].ln1_w, W.dec[l + 1].ln1_b, F.w2, F.s2);
-        else if (fused) resid(dff, 4 * d, Lw.w2, Lw.b2, W.lnd_w, W.lnd_b, F.w2, F.s2);  // dh = final LN of every row
-        else resid(dff, 4 * d, Lw.w2, Lw.b2, nullptr, nullptr);
+        resid(r.datt, d, Lw.wxo, Lw.bxo, Lw.ln2_w, Lw.ln2_b);
+        gemm(EPI_GELU, gemm_plain(r.dh, n, d, Lw.w1, 4 * d, Lw.b1, r.dff, 4 * d));
+        if (l + 1 < L) resid(r.dff, 4 * d, Lw.w2, Lw.b2, W.dec[l + 1].ln1_w, W.dec[l + 1].ln1_b);
+        else resid(r.dff, 4 * d, Lw.w2, Lw.b2, nullptr, nullptr);
     }
-    if (fused) {
-        gemm(KCLS, EPI_F32, gemm_plain(dh, n_tok, d, W.tok_emb, V, nullptr, w.logits + (size_t)v.r0 * V, V));
-    } else {
-        launch_layernorm(dt, w.dx, w.lrows, n_rows, d, W.lnd_w, W.lnd_b, w.lrow, st);
-        gemm(KCLS, EPI_F32, gemm_plain(w.lrow, n_rows, d, W.tok_emb, V, nullptr, w.logits, V));
-    }
+    launch_layernorm(dt, w.dx, w.lrows, n_rows, d, W.lnd_w, W.lnd_b, w.lrow, st);
+    gemm(EPI_F32, gemm_plain(w.lrow, n_rows, d, W.tok_emb, V, nullptr, w.logits, V));
 }
-
-// Row groups of a decode step. The fused pass (every LayerNorm folded into a split-K reduce) takes at
-// most 128 rows, so a step over n > 128 clips runs as ceil(n / 128) fused groups of near-equal size,
-// alternating between the state's two streams (forked from and joined back into the state's stream:
-// branches of the step's hipGraph); two groups for 129..256 clips measured the same as the unfused
-// path in bf16 (turbo at 256 clips: decode 213 vs 217 ms per step) and the fp8 decoder weights exist
-// only on the fused path.
-// Splitting steps of 32..128 clips into two concurrent groups measured slower on large-v3 at 128 clips
-// (2360-2392 vs 2729-2740 audio-s/s: the cross-attention pass at 64 clips per group reads E at 3.6
-// instead of 4.7 TB/s), and so did two separate graphs on two streams (942 vs 843 ms of decode per
-// step, profiles/r02_dec_groups_ab.txt); both were removed.
-static int dec_groups(int n_tok) { return cdiv(n_tok, 128); }
 
 // The two stream halves of a decode step's scratch: group views on the state's stream use the first
 // half of the split-K slabs and cross-attention partials, views on stream2 the second. A group of
@@ -1266,21 +1317,25 @@ static void dec_halves(Context* c, whisper_state* s, int gmax, bool xdirect, Dec
                 w.xml ? w.xml + xoff * H * 2 : nullptr};
 }
 
-static void decoder_launch(Context* c, whisper_state* s, int n_tok, int n_rows, bool rows_identity, bool xdirect) {
+// One row group of a decode step on the plan's path for it; self_share: its share of the step's self-attention work
+static void decoder_group(Context* c, whisper_state* s, const DecView& v, const StepPlan& P, double self_share) {
+    switch (v.n == P.gsz ? P.path : P.tail_path) {
+    case STEP_PDEC: decoder_rows_pdec(c, s, v, P.pipe); break;
+    case STEP_SMALL: decoder_rows_small(c, s, v, P.xdirect, self_share); break;
+    case STEP_SPLITK: decoder_rows_step(c, s, v, P, self_share); break;
+    }
+}
+
+// The decode step the plan describes (token metadata already on the device); kernels only (graph-capturable)
+static void decoder_launch(Context* c, whisper_state* s, const StepPlan& P) {
     Workspace& w = s->ws;
-    const bool step = rows_identity && n_rows == n_tok;  // a decode step: one token per clip, logits of every row
-    const int groups = step ? dec_groups(n_tok) : 1;
-    s->step_rows = n_tok;
-    if (groups == 1) {
-        // prefill / language detection / whisper_decode: the unfused pass over the tiles that
-        // decoder_upload built (decoder_forward); decode steps of <= 128 clips: one fused pass
-        const DecView v{0, n_tok, s->stream, w.splitk, w.splitk_elems, w.xo, w.xml};
-        decoder_rows(c, s, v, n_rows, step, xdirect, 1.0);
+    const int n_tok = P.n, gsz = P.gsz;
+    if (P.groups == 1) {
+        decoder_group(c, s, DecView{0, n_tok, s->stream, w.splitk, w.splitk_elems, w.xo, w.xml}, P, 1.0);
         return;
     }
-    const int gsz = cdiv(n_tok, groups);
     DecView half[2];
-    dec_halves(c, s, gsz, xdirect, half[0], half[1]);
+    dec_halves(c, s, gsz, P.xdirect, half[0], half[1]);
     // block-quantized files before the expanded copy exists: one dequantization scratch per state, so
     // the groups run one after the other on the state's stream
     if (c->quant && !c->expanded.load(std::memory_order_acquire)) half[1] = half[0];
@@ -1290,7 +1345,7 @@ static void decoder_launch(Context* c, whisper_state* s, int n_tok, int n_rows, 
         DecView v = half[g & 1];
         v.r0 = r0;
         v.n = std::min(gsz, n_tok - r0);
-        decoder_rows(c, s, v, v.n, true, xdirect, (double)v.n / n_tok);
+        decoder_group(c, s, v, P, (double)v.n / n_tok);
     }
     WM_CHECK(hipEventRecord(s->ev_join, s->stream2));
     WM_CHECK(hipStreamWaitEvent(s->stream, s->ev_join, 0));
@@ -1342,10 +1397,12 @@ static bool choose_xdirect(Context* c, whisper_state* s, int n_tok) {
     return false;
 }
 
-static void decoder_forward(Context* c, whisper_state* s, int n_tok, int n_rows, bool rows_identity = false) {
+// prefill / language detection / whisper_decode: the unfused pass over the tiles that decoder_upload builds
+static void decoder_forward(Context* c, whisper_state* s, int n_tok, int n_rows) {
+    Workspace& w = s->ws;
     const bool xdirect = choose_xdirect(c, s, n_tok);
     decoder_upload(c, s, n_tok, n_rows, true);
-    decoder_launch(c, s, n_tok, n_rows, rows_identity, xdirect);
+    decoder_rows_prefill(c, s, DecView{0, n_tok, s->stream, w.splitk, w.splitk_elems, w.xo, w.xml}, n_rows, xdirect);
 }
 
 int decode_tokens(Context* c, whisper_state* s, const int* tokens, const int* pos, const int* slots, int n_tok,
@@ -1735,8 +1792,7 @@ static void align_windows(Sched& S) {
         decoder_upload(c, s, nt, 0, true);
         const AlignPass al{w.al_clips, ng, max_rows, nt, w.al_P};
         const DecView dv{0, nt, st, w.splitk, w.splitk_elems, w.xo, w.xml};
-        s->step_rows = nt;
-        decoder_rows(c, s, dv, 0, false, false, 1.0, &al);
+        decoder_rows_prefill(c, s, dv, 0, false, &al);
         {
             KT kt(s, K_ALIGN_COST, (double)p_el * 4 * 3);
             launch_align_cost(w.al_P, w.al_clips, ng, (int)A, max_n, max_f, w.al_stats, w.al_cost, st);
@@ -1892,11 +1948,13 @@ static const unsigned* pd_err_ptr(Context* c, whisper_state* s, int pd) {
 }
 static size_t ring_slot_bytes(const Workspace& w) { return (size_t)w.cap_jobs * sizeof(TokOut) + 16; }
 
-// The decode graph of n rows on the state's current path (pd: 0 launch chain, 1 persistent step, 2 batched
-// chain), instance `par` (captured on first use; graphs of a persistent path captured under an older stamps
-// pointer / spin limit are retired first). par 0: the per-step path's; par 1, 2: the pipelined path's two
-// instances, which end with the device-side advance writing the step's results to ring slot par - 1.
-static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, int n, int pd, int par) {
+// The decode graph of the planned step (keyed by its rows and pd: 0 launch chain, 1 persistent step), instance
+// `par` (captured on first use; graphs of a persistent path captured under an older stamps pointer / spin
+// limit are retired first). par 0: the per-step path's; par 1, 2: the pipelined path's two instances, which
+// end with the device-side advance writing the step's results to ring slot par - 1.
+static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan P, int par) {
+    const int n = P.n, pd = P.path == STEP_PDEC;
+    P.pipe = par > 0;
     const int sig = dec_path_sig();
     // read once: a setter stores its value before it bumps the generation, so a graph captured below under
     // generation `gen` holds that generation's (or a newer) stamps pointer and spin limit, and is retired later
@@ -1918,11 +1976,9 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, int n, i
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, nullptr, {}};
     hipGraph_t graph;
     s->capture_ev = &g.ev;
-    s->pipe_capture = par > 0;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    decoder_launch(c, s, n, n, true, s->direct);
+    decoder_launch(c, s, P);
     logits_launch(c, s, n);
-    s->pipe_capture = false;
     if (par > 0) {
         Workspace& w = s->ws;
         char* slot = w.ring + (par - 1) * ring_slot_bytes(w);
@@ -1965,13 +2021,34 @@ struct PdecRunLock {
     }
 };
 
-// the decode path of a step of n rows (and its buffers prepared)
-static int dec_path_prepare(Context* c, whisper_state* s, int n) {
+// the plan of a step of n rows, with the state's backoff frozen for the step (step_variant and the step's
+// graph see the same pdec_off) and the persistent path's buffers prepared
+static StepPlan dec_path_prepare(Context* c, whisper_state* s, int n) {
     s->pdec_off = s->pdec_give_ups > 0 && now_ms() < s->pdec_off_until;
-    s->step_rows = n;
-    const int pd = pdec_use(c, s, n, s->direct) ? 1 : 0;
-    if (pd) pdec_prepare(c, s);
-    return pd;
+    const StepPlan P = step_plan(c, s, n, s->direct);
+    if (P.path == STEP_PDEC) pdec_prepare(c, s);
+    return P;
+}
+
+// The persistent launch of a step of n rows gave up (a wait timed out: not every workgroup became
+// resident): the step again on the per-kernel path from the inputs on the device, which rewrites
+// everything the launch may have written (the self K/V rows of this position); results in w.h_tout.
+// Counted (whisper_mi355x_pdec_give_ups; t0: when the step began) and followed by kPdecBackoffMs of steps
+// on the per-kernel path.
+static void rerun_given_up(Sched& S, int n, bool any_probs, std::vector<std::vector<float>>& probs_rows, double t0) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    static bool warned = false;
+    if (!warned) fprintf(stderr, "whisper_mi355x: persistent decode step timed out; step re-run on the per-kernel path\n");
+    warned = true;
+    *s->ws.h_pd_err = 0;
+    decoder_launch(c, s, step_plan(c, s, n, s->direct, false));
+    logits_launch(c, s, n);
+    logits_finish(S, n, any_probs, probs_rows);
+    s->pdec_give_ups++;
+    g_pdec_give_ups_total++;
+    s->pdec_off_until = now_ms() + kPdecBackoffMs;
+    s->pdec_lost_ms += now_ms() - t0;
 }
 
 static void decode_step(Sched& S, const std::vector<int>& act, std::vector<std::vector<float>>& probs_rows) {
@@ -1981,17 +2058,16 @@ static void decode_step(Sched& S, const std::vector<int>& act, std::vector<std::
     decoder_upload(c, s, n, n, false);
     const bool any = logits_prepare(S, act, false);
     const double t_step = now_ms();
-    const int pd = dec_path_prepare(c, s, n);
-    whisper_state::DecGraph* G = dec_graph(c, s, n, pd, 0);
+    whisper_state::DecGraph* G = dec_graph(c, s, dec_path_prepare(c, s, n), 0);
     if (!G->pdec) {
         WM_CHECK(hipGraphLaunch(G->exec, s->stream));
         logits_finish(S, n, any, probs_rows);
         kt_flush_graph(s, *G);
         return;
     }
-    // A persistent launch (the one-launch step, or the chain's launches) needs its 256 workgroups resident
-    // together: persistent steps of different states (threads) of this process on one device never overlap,
-    // so two of them cannot hold half the CUs each (steps on different devices do not wait for each other)
+    // A persistent launch needs its 256 workgroups resident together: persistent steps of different states
+    // (threads) of this process on one device never overlap, so two of them cannot hold half the CUs each
+    // (steps on different devices do not wait for each other)
     bool gave_up;
     {
         PdecRunLock lk(c->device);
@@ -2000,29 +2076,7 @@ static void decode_step(Sched& S, const std::vector<int>& act, std::vector<std::
         gave_up = *s->ws.h_pd_err != 0;
     }
     kt_flush_graph(s, *G);
-    if (!gave_up) return;
-    // the launch gave up (a wait timed out: not every workgroup became resident): the step again on
-    // the per-kernel path, which rewrites everything the launch may have written (the self K/V rows of
-    // this position); counted (whisper_mi355x_pdec_give_ups) and followed by kPdecBackoffMs of steps on
-    // the per-kernel path
-    static bool warned = false;
-    if (!warned) fprintf(stderr, "whisper_mi355x: persistent decode step timed out; step re-run on the per-kernel path\n");
-    warned = true;
-    *s->ws.h_pd_err = 0;
-    s->pdec_block = true;
-    try {
-        decoder_launch(c, s, n, n, true, s->direct);
-        logits_launch(c, s, n);
-        logits_finish(S, n, any, probs_rows);
-    } catch (...) {
-        s->pdec_block = false;
-        throw;
-    }
-    s->pdec_block = false;
-    s->pdec_give_ups++;
-    g_pdec_give_ups_total++;
-    s->pdec_off_until = now_ms() + kPdecBackoffMs;
-    s->pdec_lost_ms += now_ms() - t_step;
+    if (gave_up) rerun_given_up(S, n, any, probs_rows, t_step);
 }
 
 // Pipelined greedy decoding. The per-step path waits for a step's 32-byte results before it launches the next
@@ -2064,7 +2118,7 @@ static bool pipe_ok(Sched& S, const std::vector<int>& act) {
 // 128-row groups (dec_groups). Equal keys: a row's results at n and at n' rows are the same bits.
 static long step_variant(Context* c, whisper_state* s, int n) {
     const int pd = pdec_use(c, s, n, s->direct) ? 1 : 0;
-    const bool small = (c->quant && n <= quant_small_max()) || n <= small_m_max();
+    const bool small = n <= small_rows_max(c);  // deliberately coarser than step_plan's test (no w8, no gemm_small_ok)
     const bool wide = !s->direct && n <= attn_cross_wide_max();
     const int sp = s->direct ? xattn_splits(n, c->hp.n_audio_ctx) : 0;
     const bool lg64 = n <= 64;
@@ -2084,37 +2138,16 @@ static void step_inputs(Sched& S, const std::vector<int>& act) {
     }
 }
 
-// Re-run the step of the `act` rows on the per-kernel path after its persistent launch gave up (the device
-// inputs as uploaded by `upload`); results in w.h_tout. Counted like decode_step's give-ups.
-static void pipe_give_up(Sched& S, const std::vector<int>& act, bool upload, double t0) {
-    Context* c = S.c;
-    whisper_state* s = S.s;
+// A pipelined step of the `act` rows gave up: the device's inputs again from the host's (the graphs' own
+// advance has moved them on), then the re-run
+static void pipe_give_up(Sched& S, const std::vector<int>& act, double t0) {
     const int n = (int)act.size();
-    WM_CHECK(hipStreamSynchronize(s->stream));
-    static bool warned = false;
-    if (!warned) fprintf(stderr, "whisper_mi355x: persistent decode step timed out; step re-run on the per-kernel path\n");
-    warned = true;
-    if (upload) {
-        step_inputs(S, act);
-        decoder_upload(c, s, n, n, false);
-        logits_prepare(S, act, false);
-    }
-    *s->ws.h_pd_err = 0;
+    WM_CHECK(hipStreamSynchronize(S.s->stream));
+    step_inputs(S, act);
+    decoder_upload(S.c, S.s, n, n, false);
+    logits_prepare(S, act, false);
     std::vector<std::vector<float>> probs_rows;
-    s->pdec_block = true;
-    try {
-        decoder_launch(c, s, n, n, true, s->direct);
-        logits_launch(c, s, n);
-        logits_finish(S, n, false, probs_rows);
-    } catch (...) {
-        s->pdec_block = false;
-        throw;
-    }
-    s->pdec_block = false;
-    s->pdec_give_ups++;
-    g_pdec_give_ups_total++;
-    s->pdec_off_until = now_ms() + kPdecBackoffMs;
-    s->pdec_lost_ms += now_ms() - t0;
+    rerun_given_up(S, n, false, probs_rows, t0);
 }
 
 // Decode the `act` jobs step after step with the next step in flight while the host processes the last one,
@@ -2139,10 +2172,11 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
     step_inputs(S, act);
     decoder_upload(c, s, n, n, false);
     logits_prepare(S, act, false);
-    const int pd = dec_path_prepare(c, s, n);
-    dec_graph(c, s, n, pd, 1);
-    dec_graph(c, s, n, pd, 2);  // (may grow dec_graphs: the pointers are taken after both exist)
-    whisper_state::DecGraph* G[2] = {dec_graph(c, s, n, pd, 1), dec_graph(c, s, n, pd, 2)};
+    const StepPlan P = dec_path_prepare(c, s, n);
+    const int pd = P.path == STEP_PDEC;
+    dec_graph(c, s, P, 1);
+    dec_graph(c, s, P, 2);  // (may grow dec_graphs: the pointers are taken after both exist)
+    whisper_state::DecGraph* G[2] = {dec_graph(c, s, P, 1), dec_graph(c, s, P, 2)};
     PdecRunLock lk(c->device, pd != 0);
     double t_step = now_ms();
     WM_CHECK(hipGraphLaunch(G[0]->exec, st));
@@ -2172,7 +2206,7 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
         const TokOut* out = (const TokOut*)hslot;
         if (pd && *(const unsigned*)(hslot + (size_t)w.cap_jobs * sizeof(TokOut))) {
             // step k gave up: re-run it on the per-kernel path from the host's inputs, then leave
-            pipe_give_up(S, act, true, t_step);
+            pipe_give_up(S, act, t_step);
             for (int r = 0; r < n; r++) S.jobs[act[r]].step++;
             for (int r = 0; r < n; r++) {
                 Job& j = S.jobs[act[r]];
@@ -2216,7 +2250,7 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
             if (pd && *(const unsigned*)(w.h_ring + (par ^ 1) * slot_b + (size_t)w.cap_jobs * sizeof(TokOut))) {
                 // its persistent launch gave up: the step again, for all n rows, from the host's inputs (the
                 // graph's own advance has moved the device's past step k + 1)
-                pipe_give_up(S, act, true, now_ms());
+                pipe_give_up(S, act, now_ms());
             }
             for (int r : still) {
                 Job& j = S.jobs[act[r]];
@@ -2523,15 +2557,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
             } else if (!act.empty()) {
                 if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
                 const double td = now_ms();
-                int* hi = w.h_ints;
                 const int na = (int)act.size();
-                for (int r = 0; r < na; r++) {
-                    Job& j = S.jobs[act[r]];
-                    hi[r] = j.tokens.back().id;
-                    hi[w.cap_tok + r] = (int)j.prompt.size() + j.step;
-                    hi[2 * w.cap_tok + r] = j.slot;
-                    hi[5 * w.cap_tok + r] = r;
-                }
+                step_inputs(S, act);
                 decode_step(S, act, probs_rows);
                 S.t_decode += now_ms() - td;
                 for (int r = 0; r < na; r++) S.jobs[act[r]].step++;

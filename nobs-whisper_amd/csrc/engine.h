@@ -179,7 +179,6 @@ struct Workspace {
     void* lrec = nullptr;  // split logits kernel: per-chunk records
     int *win_job = nullptr, *win_seek = nullptr, *win_slot = nullptr;
     // persistent decode step: the hand-off block (granules + error word) and the error word's host copy
-    // (shared with the batched chain's error word)
     unsigned* pd_sync = nullptr;
     unsigned* h_pd_err = nullptr;
     // pipelined greedy decoding (engine.cpp decode_pipelined): two ring slots of [cap_jobs TokOut][16-byte error
@@ -270,18 +269,15 @@ struct whisper_state {
     struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; hipGraphExec_t exec; std::vector<KPending> ev; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
-    bool pipe_capture = false;  // capturing a pipelined step graph (its advance kernel copies the error word)
     double cur_self_work = 0;                     // self-attention bytes of the current step
     whisper_state* twin = nullptr;                // second half of a paired batch (full_batch)
-    bool pdec_block = false;                      // re-running a step whose persistent launch gave up
-    int step_rows = 0;                            // rows of the decode step being built (all row groups)
     // persistent launches of this state that gave up (a wait timed out: not all 256 workgroups resident, e.g.
     // beside another process's kernels) and were re-run on the per-kernel path; after one, the state's steps
     // take the per-kernel path for kPdecBackoffMs (pdec_off) instead of paying the timeout on every step
     long pdec_give_ups = 0;
     double pdec_lost_ms = 0;    // wall time of the given-up launches (wait until give-up + the re-run)
     double pdec_off_until = 0;  // now_ms() clock
-    bool pdec_off = false;
+    bool pdec_off = false;      // the backoff as frozen once per step (dec_path_prepare), so its plan, graph and step_variant agree
 };
 
 struct whisper_context {

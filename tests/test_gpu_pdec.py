@@ -12,7 +12,8 @@ cross K/V cache form.
   * a batch of 4 clips (the largest it takes) against the oracle clip by clip;
   * the give-up path: with a zero spin limit every launch gives up and the step is re-run on the
     per-kernel path: results equal the per-kernel path's (WHISPER_MI355X_PDEC=0) bit for bit, and the
-    state's give-up counter says so (every other case asserts it is 0);
+    state's give-up counter says so (every other case asserts it is 0); the same for a pipelined step
+    (WHISPER_MI355X_PIPE_MIN=0: the first decode step is already pipelined);
   * batch == single on the default path (3 clips of different lengths: persistent steps at 3, 2, 1 clips);
   * two states on two host threads (persistent steps serialised by the engine): each equals its
     single-threaded run.
@@ -169,6 +170,30 @@ def test_pdec_give_up_reruns_step(wrs, monkeypatch, capfd, dtype):
         L.whisper_mi355x_set_pdec_spin(5000000)
     # the first launch gives up and is re-run; the state's next steps then take the per-kernel path for
     # the backoff period instead of timing out again (kernel stats count the give-ups)
+    assert n1[0] > 0 and n1[1] >= 1, n1
+    assert forced == plain
+
+
+def test_pdec_give_up_reruns_pipelined_step(wrs, monkeypatch):
+    """The same with WHISPER_MI355X_PIPE_MIN=0, so that the first decode step is already pipelined: its
+    persistent launch gives up, the pipelined path re-runs the step on the per-kernel path from the host's
+    inputs and leaves; the results are those of WHISPER_MI355X_PDEC=0 exactly."""
+    from conftest import model_path
+    monkeypatch.setenv("WHISPER_MI355X_CROSS", "cache")
+    monkeypatch.setenv("WHISPER_MI355X_STATE_POOL", "0")
+    monkeypatch.setenv("WHISPER_MI355X_PIPE_MIN", "0")
+    path = model_path("tiny+conf")
+    clips = [synthetic_pcm(k) for k in range(2)]
+    L = wrs.lib()
+    monkeypatch.setenv("WHISPER_MI355X_PDEC", "0")
+    plain, n0 = _run(wrs, path, clips, wrs.F16)
+    assert n0 == (0, 0)
+    monkeypatch.delenv("WHISPER_MI355X_PDEC")
+    L.whisper_mi355x_set_pdec_spin(0)
+    try:
+        forced, n1 = _run(wrs, path, clips, wrs.F16)
+    finally:
+        L.whisper_mi355x_set_pdec_spin(5000000)
     assert n1[0] > 0 and n1[1] >= 1, n1
     assert forced == plain
 
