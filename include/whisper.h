@@ -26,6 +26,11 @@
  * whisper-rs-sys's generated bindings offline (SURVEY.md §7 hard part (i)). Functions of the
  * upstream header that this engine does not implement are exported as stubs that return an
  * error value, so a static link of whisper-rs resolves.
+ *
+ * Both sampling strategies are implemented. WHISPER_SAMPLING_BEAM_SEARCH (whisper-rs SamplingStrategy::BeamSearch)
+ * keeps beam_size <= 8 hypotheses per window at t = 0 and extends each by its beam_size most probable tokens after
+ * the logits rules, where upstream draws them from the softmax; patience is accepted and ignored; attempts at t > 0
+ * are single sampled decoders, as with the greedy strategy (whisper_mi355x.h).
  */
 #ifndef WHISPER_H
 #define WHISPER_H

@@ -45,7 +45,14 @@ WHISPER_API int whisper_mi355x_broadcast_weights(struct whisper_context * ctx, c
  * f32 samples, on the host (pcm_on_device = false) or already in this context's HBM (true).
  * Fixed-work benchmark mode: fixed_tokens > 0 decodes exactly that many tokens per window with EOT
  * suppressed and no temperature fallback; at most n_text_ctx / 2 - 4 (a window's limit,
- * 220), else -1. Returns 0 on success. */
+ * 220), else -1. Returns 0 on success.
+ * Beam search (params.strategy = WHISPER_SAMPLING_BEAM_SEARCH, here and in whisper_full*): the t = 0 attempt of
+ * every window decodes beam_size hypotheses per clip, each beam's candidates being its beam_size most probable
+ * tokens after the logits rules (upstream samples them); attempts at t > 0 are single sampled
+ * decoders as with the greedy strategy, and patience is ignored. beam_size < 1 counts as 1 (the greedy result,
+ * bit for bit), beam_size > 8 returns -4. With beam_size > 1 every live beam of every clip is one row of a
+ * cache-form decode step: n_jobs * beam_size <= 32, else -1 (one stderr line). fixed_tokens > 0 with the beam
+ * strategy returns -1. */
 WHISPER_API int whisper_mi355x_full_batch(struct whisper_context * ctx, struct whisper_state * state,
                                           struct whisper_full_params params, const float * const * pcm,
                                           const int * n_samples, int n_jobs, bool pcm_on_device, int fixed_tokens);
@@ -59,6 +66,15 @@ WHISPER_API int whisper_mi355x_full_batch_forced(struct whisper_context * ctx, s
                                                  struct whisper_full_params params, const float * const * pcm,
                                                  const int * n_samples, int n_jobs, bool pcm_on_device, int fixed_tokens,
                                                  const int * forced, const int * spot, int n_spot, float * spot_logits);
+/* Beam `beam` of the last beam-searched window (the t = 0 attempt) of job `job` of the last full / full_batch call
+ * (job 0 for whisper_full_with_state): its tokens as decoded (before the cut at result_len; at most cap are
+ * copied), its sum of token log-probabilities, and flags: bit 0 completed, bit 1 failed, bit 2 the window's
+ * winner. Returns the token count, or -1 when there is no such beam (greedy strategy, no window decoded). */
+#define WHISPER_MI355X_BEAM_COMPLETED 1
+#define WHISPER_MI355X_BEAM_FAILED 2
+#define WHISPER_MI355X_BEAM_WINNER 4
+WHISPER_API int whisper_mi355x_beam_info(struct whisper_state * state, int job, int beam, int * tokens, int cap,
+                                         double * sum_logprobs_all, int * flags);
 WHISPER_API int whisper_mi355x_batch_n_segments(struct whisper_state * state, int job);
 WHISPER_API const char * whisper_mi355x_batch_segment_text(struct whisper_state * state, int job, int i_segment);
 WHISPER_API int64_t whisper_mi355x_batch_segment_t0(struct whisper_state * state, int job, int i_segment);
@@ -127,7 +143,8 @@ WHISPER_API int whisper_mi355x_get_encoder_out(struct whisper_state * state, flo
  * roofline). Classes: 0 encoder-side GEMM (work = FLOPs), 1 encoder attention (FLOPs),
  * 2 decoder cross-attention (HBM bytes), 3 decoder self-attention (bytes), 4 decoder GEMM (bytes),
  * 5 logits processing (bytes), 6 mel (bytes), 7 the persistent decode step (bytes), 8 prefill attention
- * (bytes), 9 / 10 / 11 the token-timestamp alignment's score (FLOPs), cost (bytes) and DTW (bytes) kernels.
+ * (bytes), 9 / 10 / 11 the token-timestamp alignment's score (FLOPs), cost (bytes) and DTW (bytes) kernels,
+ * 12 beam search's top-k logits kernel (bytes), 13 its self-cache gather (bytes read + written).
  * class_mask bit k times class k (0 = off); bits 16..23, when > 1, time
  * the decoder's per-layer attention launches (classes 2, 3) of every k-th layer only.
  * Every call resets the counters; stats out = {total ms, launches, total work}. */
@@ -141,6 +158,10 @@ WHISPER_API int whisper_mi355x_kernel_stats(struct whisper_state * state, int cl
  * state of the process). */
 #define WHISPER_MI355X_KSTAT_PDEC_GIVE_UPS 100
 WHISPER_API long whisper_mi355x_pdec_give_ups(struct whisper_state * state);
+/* Pseudo class of whisper_mi355x_kernel_stats: out = {bytes the self-cache gather of beam search copied on this
+ * state since it was created (or recycled), the bytes whole-sequence copies would have been (no common-prefix
+ * rule), 0}. Not reset by whisper_mi355x_kernel_timing. */
+#define WHISPER_MI355X_KSTAT_BEAM_GATHER 101
 
 /* Kernel-level test/tuning hooks (device pointers): one fused-epilogue GEMM launch of the engine
  * (epi as in kernels.h: 0 store, 1 gelu, 2 residual f32, 4 f32, 5 cross K/V: out is then a cross cache of
@@ -239,6 +260,28 @@ WHISPER_API int whisper_mi355x_debug_attn_prefill(struct whisper_context * ctx, 
                                                   const void * cache, const int * slot, const int * n_kv,
                                                   const void * tiles, int n_tiles, int L, int layer, int H, int n_ctx,
                                                   void * out);
+
+/* Debug: beam search's two kernels on caller data.
+ * logits_topk: logits = n device rows [n][n_vocab] (f32, the context's vocabulary); rules = host [n][10] ints per row
+ * {is_initial, last_ts, penult_ts, has_ts, seek_delta, suppress_blank, no_timestamps, suppress_eot, tid0_initial
+ * (< 0: no max_initial_ts rule), want_nosp}, temperature = host [n] (NULL: 0). k <= 8 candidates per row go to
+ * cand (host [n][k]; rank order; id = -1: fewer tokens have p > 0), and greedy (host [n]) receives what the greedy
+ * logits launch returns for the same rows in the same form. split = 1: the form the engine takes for this row
+ * count (the split form up to 16 rows), 0: one workgroup per row.
+ * kv_gather: cache = device [n_slots][L][2][H][n_ctx][64] of 2-byte elements; copies = host [n_copies][4] ints
+ * {dst_slot, src_slot, row0, row1}: rows [row0, row1) of K and V of every layer and head move from src to dst as a
+ * parallel assignment (every copy reads the cache as it was before). Destinations must be distinct.
+ * *n_staged (optional) = copies that went through the staging buffer. Return 0, -1 on bad arguments, or the runtime
+ * error code when the launcher refuses the list (nothing is launched). */
+struct whisper_mi355x_cand {
+    int32_t id, tid;
+    float   p, plog, pt, ptsum, no_speech_prob, pad;
+};
+WHISPER_API int whisper_mi355x_debug_logits_topk(struct whisper_context * ctx, const float * logits, int n,
+                                                 const int * rules, const float * temperature, int k, int split,
+                                                 struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy);
+WHISPER_API int whisper_mi355x_debug_kv_gather(struct whisper_context * ctx, void * cache, int n_slots, int L, int H,
+                                               int n_ctx, const int * copies, int n_copies, int * n_staged);
 
 /* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
  * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.

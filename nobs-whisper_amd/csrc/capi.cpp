@@ -4,6 +4,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include <rccl/rccl.h>
 
@@ -475,6 +476,15 @@ int whisper_mi355x_full_batch_forced(struct whisper_context* ctx, struct whisper
     o.spot_logits = spot_logits;
     return guarded(s, [&] { return full_batch(&ctx->c, s, p, pcm, n, n_jobs, on_device, o, false); });
 }
+int whisper_mi355x_beam_info(struct whisper_state* s, int job, int beam, int* tokens, int cap, double* sum_logprobs_all,
+                             int* flags) {
+    if (!s || job < 0 || job >= (int)s->beam_info.size() || beam < 0 || beam >= (int)s->beam_info[job].size()) return -1;
+    const whisper_state::BeamRec& r = s->beam_info[job][beam];
+    for (int i = 0; tokens && i < cap && i < (int)r.tokens.size(); i++) tokens[i] = r.tokens[i];
+    if (sum_logprobs_all) *sum_logprobs_all = r.sum_logprobs_all;
+    if (flags) *flags = r.flags;
+    return (int)r.tokens.size();
+}
 int whisper_mi355x_batch_n_segments(struct whisper_state* s, int job) {
     return s && job >= 0 && job < (int)s->results.size() ? (int)s->results[job].size() : 0;
 }
@@ -569,6 +579,14 @@ int whisper_mi355x_kernel_stats(struct whisper_state* s, int cls, double out[3])
     if (s && cls == WHISPER_MI355X_KSTAT_PDEC_GIVE_UPS) {
         out[0] = s->pdec_lost_ms;
         out[1] = (double)s->pdec_give_ups;
+        out[2] = 0.0;
+        return 0;
+    }
+    if (s && cls == WHISPER_MI355X_KSTAT_BEAM_GATHER && s->ctx) {
+        const Hparams& hp = s->ctx->hp;
+        const double row_bytes = (double)hp.n_text_layer * 2 * hp.n_text_head * 128;
+        out[0] = s->gather_rows * row_bytes;
+        out[1] = s->gather_rows_full * row_bytes;
         out[2] = 0.0;
         return 0;
     }
@@ -886,6 +904,77 @@ int whisper_mi355x_debug_attn_cross_step(struct whisper_context* ctx, const floa
         hipStream_t st = hs.st;
         launch_attn_cross_step(ctx->c.dt, sl, cache, slot, n_kv, n, L, layer, H, n_ctx, d, out, st);
         WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+// ---- beam search's kernels on caller data (kernels/logits.hip top-k forms, kernels/beam.hip) ---------------------
+// device buffers of a hook, freed also when a launcher throws
+struct HookBufs {
+    std::vector<void*> p;
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        WM_CHECK(hipMalloc(&q, bytes));
+        p.push_back(q);
+        return q;
+    }
+    ~HookBufs() { for (void* q : p) hipFree(q); }
+};
+static_assert(sizeof(whisper_mi355x_cand) == sizeof(TokOut), "whisper_mi355x_cand mirrors TokOut");
+int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* logits, int n, const int* rules,
+                                     const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,
+                                     struct whisper_mi355x_cand* greedy) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !logits || !rules || !cand || !greedy || n <= 0 || k < 1 || k > kTopkMax) return -1;
+        hipSetDevice(ctx->c.device);
+        const int V = ctx->c.hp.n_vocab;
+        std::vector<SeqCtl> ctl(n);
+        for (int r = 0; r < n; r++) {
+            const int* q = rules + (size_t)r * 10;
+            ctl[r] = SeqCtl{q[0], q[1], q[2], q[3], q[4], temperature ? temperature[r] : 0.0f, q[5], q[6], q[7], q[8], 0, q[9]};
+        }
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        SeqCtl* d_ctl = (SeqCtl*)b.get(n * sizeof(SeqCtl));
+        TokOut* d_out = (TokOut*)b.get((size_t)n * (kTopkMax + 1) * sizeof(TokOut));
+        void* rec = split ? b.get(logits_rec_bytes(n)) : nullptr;
+        WM_CHECK(hipMemcpyAsync(d_ctl, ctl.data(), n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
+        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out + (size_t)n * kTopkMax, nullptr, rec, st);
+        launch_logits_topk(logits, V, d_ctl, n, ctx->c.vid, d_out, k, rec, st);
+        std::vector<TokOut> out((size_t)n * (kTopkMax + 1));
+        WM_CHECK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        for (int r = 0; r < n; r++) {
+            memcpy(&greedy[r], &out[(size_t)n * kTopkMax + r], sizeof(TokOut));
+            for (int q = 0; q < k; q++) memcpy(&cand[(size_t)r * k + q], &out[(size_t)r * kTopkMax + q], sizeof(TokOut));
+        }
+        return 0;
+    });
+}
+int whisper_mi355x_debug_kv_gather(struct whisper_context* ctx, void* cache, int n_slots, int L, int H, int n_ctx,
+                                   const int* copies, int n_copies, int* n_staged) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !cache || !copies || n_copies < 0 || n_slots <= 0 || L <= 0 || H <= 0 || n_ctx <= 0) return -1;
+        if (n_staged) *n_staged = 0;
+        if (n_copies == 0) return 0;
+        hipSetDevice(ctx->c.device);
+        std::vector<KvCopy> cp(n_copies);
+        for (int i = 0; i < n_copies; i++) {
+            cp[i] = KvCopy{copies[4 * i], copies[4 * i + 1], copies[4 * i + 2], copies[4 * i + 3], 0, 0, 0};
+            for (int q = 0; q < i; q++)
+                if (cp[q].dst_slot == cp[i].dst_slot) return -1;
+        }
+        const long need = beam_schedule(cp, (long)L * 2 * H * 8);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        KvCopy* d_cp = (KvCopy*)b.get(n_copies * sizeof(KvCopy));
+        void* stage = need > 0 ? b.get((size_t)need * 16) : nullptr;
+        WM_CHECK(hipMemcpyAsync(d_cp, cp.data(), n_copies * sizeof(KvCopy), hipMemcpyHostToDevice, st));
+        launch_kv_gather(cache, n_slots, L, H, n_ctx, cp.data(), d_cp, n_copies, stage, need, st);
+        WM_CHECK(hipStreamSynchronize(st));
+        if (n_staged)
+            for (const KvCopy& c : cp) *n_staged += c.mode;
         return 0;
     });
 }

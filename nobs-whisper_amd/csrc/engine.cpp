@@ -186,6 +186,10 @@ static void reset_for_reuse(whisper_state* s) {
     s->pdec_lost_ms = 0;
     s->pdec_off_until = 0;
     s->pdec_off = false;
+    s->beam_k = 0;
+    s->split_slots = false;
+    s->beam_info.clear();
+    s->gather_rows = s->gather_rows_full = 0;
     std::fill(s->ws.cross_fresh.begin(), s->ws.cross_fresh.end(), 0);
 }
 
@@ -283,6 +287,8 @@ void recover_state(whisper_state* s) {
         }
     }
     s->capture_ev = nullptr;
+    s->beam_k = 0;  // (an error inside a beam step)
+    s->split_slots = false;
     hipStreamSynchronize(s->stream);
     hipStreamSynchronize(s->stream2);
     (void)hipGetLastError();
@@ -307,6 +313,10 @@ static void free_ws(Workspace& w) {
     dfree(w.lrow); dfree(w.logits); dfree(w.probs); dfree(w.tok); dfree(w.ctl); dfree(w.tout); dfree(w.lrec); dfree(w.win_job);
     dfree(w.pcm); dfree(w.mel); dfree(w.mel_ptrs); dfree(w.splitk); dfree(w.enc); dfree(w.qx); dfree(w.xo);
     dfree(w.xml); dfree(w.kvslot); dfree(w.hs); dfree(w.qtiles); dfree(w.wdq); dfree(w.pd_sync);
+    dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage);
+    if (w.h_sslot) hipHostFree(w.h_sslot);
+    if (w.h_cand) hipHostFree(w.h_cand);
+    if (w.h_kvcp) hipHostFree(w.h_kvcp);
     if (w.h_pd_err) hipHostFree(w.h_pd_err);
     if (w.h_ring) hipHostFree(w.h_ring);
     for (auto& e : w.ring_ev)
@@ -372,11 +382,13 @@ static void ensure_cross(Context* c, whisper_state* s, int slots) {
 // (Re)allocate the workspace for n_jobs clips. Encoder activations are sized for at most
 // enc_batch() windows at once; caches for n_jobs slots. If an allocation fails (out of memory),
 // the whole workspace is released and the error propagates: the state stays usable (empty).
-static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs) {
+// Beam search passes its decoder rows (clips x beams) as n_jobs and its clips as n_clips: the self cache and
+// the per-row buffers hold every beam, the encoder activations and the cross K/V cache only the clips.
+static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips) {
     Workspace& w = s->ws;
     const Hparams& hp = c->hp;
     const size_t d = hp.n_audio_state, nm = hp.n_mels, T = hp.n_audio_ctx, E = esize(c->dt);
-    const int n_enc = std::min(n_jobs, enc_batch());
+    const int n_enc = std::min(n_clips, enc_batch());
     if (n_enc > w.cap_enc || n_jobs > w.cap_jobs) drop_graphs(s);
     if (n_enc > w.cap_enc) {
         dfree(w.mel_img); dfree(w.h1); dfree(w.hn); dfree(w.qkv); dfree(w.att); dfree(w.ff); dfree(w.x);
@@ -407,7 +419,9 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs) {
         free_align(w);  // sized by cap_jobs
         for (auto& a : s->align_info) a = {};  // (pointers into al_cost)
         if (w.h_ring) { WM_CHECK(hipHostFree(w.h_ring)); w.h_ring = nullptr; w.ring = nullptr; }
-        for (void** h : {(void**)&w.h_qtiles, (void**)&w.h_ints, (void**)&w.h_tout, (void**)&w.h_ctl})
+        dfree(w.sslot); dfree(w.cand); dfree(w.kvcp);
+        for (void** h : {(void**)&w.h_qtiles, (void**)&w.h_ints, (void**)&w.h_tout, (void**)&w.h_ctl, (void**)&w.h_sslot,
+                         (void**)&w.h_cand, (void**)&w.h_kvcp})
             if (*h) { void* q = *h; *h = nullptr; WM_CHECK(hipHostFree(q)); }
         w.cap_jobs = w.cap_tok = w.cap_cross = w.cap_xq = 0;
         // split-K slabs: decode steps (<= 128 rows per group, two concurrent groups) and the prefill
@@ -450,6 +464,12 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs) {
         WM_CHECK(hipHostMalloc((void**)&w.h_qtiles, (size_t)n_tok * sizeof(int2), 0));
         WM_CHECK(hipHostMalloc((void**)&w.h_tout, (size_t)n_jobs * sizeof(TokOut), 0));
         WM_CHECK(hipHostMalloc((void**)&w.h_ctl, (size_t)n_jobs * sizeof(SeqCtl), 0));
+        dalloc(w.sslot, (size_t)n_jobs * sizeof(int));
+        dalloc(w.cand, (size_t)n_jobs * kTopkMax * sizeof(TokOut));
+        dalloc(w.kvcp, (size_t)n_jobs * sizeof(KvCopy));
+        WM_CHECK(hipHostMalloc((void**)&w.h_sslot, (size_t)n_jobs * sizeof(int), 0));
+        WM_CHECK(hipHostMalloc((void**)&w.h_cand, (size_t)n_jobs * kTopkMax * sizeof(TokOut), 0));
+        WM_CHECK(hipHostMalloc((void**)&w.h_kvcp, (size_t)n_jobs * sizeof(KvCopy), 0));
         w.cap_jobs = n_jobs;
         w.cap_tok = n_tok;
     }
@@ -465,13 +485,13 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs) {
         dalloc(w.xo, xo_rows * H * d * 4);
         dalloc(w.xml, xo_rows * H * 2 * 4);
     }
-    if (!s->direct) ensure_cross(c, s, n_jobs);
+    if (!s->direct) ensure_cross(c, s, n_clips);
     if (c->quant && !w.wdq) dalloc(w.wdq, (size_t)16 * d * d * E);
 }
 
-static void ensure_ws(Context* c, whisper_state* s, int n_jobs) {
+static void ensure_ws(Context* c, whisper_state* s, int n_jobs, int n_clips = -1) {
     try {
-        ensure_ws_impl(c, s, n_jobs);
+        ensure_ws_impl(c, s, n_jobs, n_clips < 0 ? n_jobs : n_clips);
     } catch (const Error&) {
         hipStreamSynchronize(s->stream);
         hipStreamSynchronize(s->stream2);
@@ -884,7 +904,7 @@ static bool pdec_blocks(Context* c) {
 // weights are f16 / bf16 or GGML blocks (not the fp8 decoder copies), the device has the 256 CUs the
 // grid is built for, and the step is in the cross K/V cache form.
 static bool pdec_use(Context* c, whisper_state* s, int n, bool xdirect) {
-    if (xdirect || s->pdec_off || n < 1 || n > pdec_max()) return false;
+    if (xdirect || s->pdec_off || s->split_slots || n < 1 || n > pdec_max()) return false;
     if (dec_fp8(c)) return false;
     // one weight form for every decoder matrix (the kernel is built per form)
     const bool quant = c->w.dec[0].qqkv.type != 0;
@@ -938,7 +958,10 @@ static StepPlan step_plan(Context* c, whisper_state* s, int n, bool xdirect, boo
     const bool pd = pdec_ok && pdec_use(c, s, n, xdirect);
     auto path = [&](int rows) {
         if (pd) return STEP_PDEC;
-        const bool small = !P.w8 && rows <= small_rows_max(c) && gemm_small_ok(rows, d, true) && gemm_small_ok(rows, 4 * d, false);
+        // (beam search with several beams per clip, split_slots: the split-K chain at every row count, so that a
+        // beam's bits do not change when other beams complete and the step's rows drop to the small-M range)
+        const bool small = !P.w8 && !s->split_slots && rows <= small_rows_max(c) && gemm_small_ok(rows, d, true) &&
+                           gemm_small_ok(rows, 4 * d, false);
         return small ? STEP_SMALL : STEP_SPLITK;
     };
     P.path = path(P.gsz);
@@ -1030,13 +1053,15 @@ struct DecRows {
     int n;
     hipStream_t st;
     int *tok, *pos, *slot, *nkv_self, *nkv_cross;
+    int* sslot;  // the rows' self-cache slots: `slot`, or the beams' own slots (whisper_state::split_slots)
     float* dx;
     void *dh, *dq, *datt, *dff, *qx;
 };
 static DecRows dec_rows(Context* c, whisper_state* s, const DecView& v) {
     Workspace& w = s->ws;
     const size_t d = c->hp.n_text_state, H = c->hp.n_text_head, E = esize(c->dt), r0 = v.r0;
-    return DecRows{v.n, v.st, w.tok + r0, w.pos + r0, w.slot + r0, w.nkv_self + r0, w.nkv_cross + r0, w.dx + r0 * d,
+    return DecRows{v.n, v.st, w.tok + r0, w.pos + r0, w.slot + r0, w.nkv_self + r0, w.nkv_cross + r0,
+                   (s->split_slots ? w.sslot : w.slot) + r0, w.dx + r0 * d,
                    (char*)w.dh + r0 * d * E, (char*)w.dq + r0 * d * E, (char*)w.datt + r0 * d * E, (char*)w.dff + r0 * 4 * d * E,
                    w.qx ? (void*)((char*)w.qx + r0 * 2 * H * d * E) : nullptr};
 }
@@ -1119,7 +1144,7 @@ static void decoder_rows_small(Context* c, whisper_state* s, const DecView& v, b
         {
             const DecSlabs sl{raw, 1, (long)n * 3 * d, 3 * d, Lw.bqkv, c->k_scale};
             KT kt(s, K_ATTN_SELF, self_share, st, kt_layer);
-            launch_attn_self_step(dt, sl, w.self, r.slot, r.pos, n, L, l, H, hp.n_text_ctx, d, r.datt, st);
+            launch_attn_self_step(dt, sl, w.self, r.sslot, r.pos, n, L, l, H, hp.n_text_ctx, d, r.datt, st);
         }
         small(Lw.qo, EPI_RESID, r.datt, d, Lw.wo, d, Lw.bo, r.dx, d);
         if (xdirect) {
@@ -1208,7 +1233,7 @@ static void decoder_rows_step(Context* c, whisper_state* s, const DecView& v, co
         {
             const DecSlabs sl = partials(r.dh, Lw.wqkv, 3 * d, Lw.bqkv, c->k_scale, F.wqkv, F.sqkv);
             KT kt(s, K_ATTN_SELF, self_share, st, kt_layer);
-            launch_attn_self_step(dt, sl, w.self, r.slot, r.pos, n, L, l, H, hp.n_text_ctx, d, r.datt, st);
+            launch_attn_self_step(dt, sl, w.self, r.sslot, r.pos, n, L, l, H, hp.n_text_ctx, d, r.datt, st);
         }
         resid(r.datt, d, Lw.wo, Lw.bo, Lw.lnx_w, Lw.lnx_b, F.wo, F.so);
         if (P.xdirect) {
@@ -1417,7 +1442,8 @@ int decode_tokens(Context* c, whisper_state* s, const int* tokens, const int* po
 }
 
 // ---- scheduler ------------------------------------------------------------------------------------
-enum Phase { PH_ENCODE, PH_LANG, PH_PREFILL, PH_DECODE, PH_DONE };
+// (PH_BEAM: the clip's t = 0 attempt decodes as beam_k hypotheses, beam_step)
+enum Phase { PH_ENCODE, PH_LANG, PH_PREFILL, PH_DECODE, PH_BEAM, PH_DONE };
 
 struct Job {
     int slot = 0;
@@ -1448,7 +1474,42 @@ struct Job {
     size_t al_seg0 = 0;
 };
 
+// Beam search: a beam is the decoder part of a Job plus its self-cache slot. The per-token code
+// (process_step, fill_ctl, score_seq) works on a Job, so a beam is swapped into its clip's Job around those calls
+// (swap_dec) and out again.
+struct Beam {
+    std::vector<TokenData> tokens;
+    int result_len = 0;
+    double sum_logprobs_all = 0, sum_logprobs = -INFINITY, avg_logprobs = -INFINITY, entropy = 0, score = -INFINITY;
+    int seek_delta = 100 * WHISPER_CHUNK_SIZE;
+    bool has_ts = false, failed = false, completed = false;
+    int step = 0;
+    bool ended = false;  // process_step said stop (completed, failed, or the window's last step)
+    int sslot = 0;
+    bool live() const { return !ended && !failed && !completed; }
+};
+struct BeamJob {
+    std::vector<Beam> beams;
+    std::vector<std::vector<int>> held;  // per beam: the tokens (prompt included) whose K/V rows its self slot holds
+};
+static void swap_dec(Job& j, Beam& b) {
+    j.tokens.swap(b.tokens);
+    std::swap(j.result_len, b.result_len);
+    std::swap(j.sum_logprobs_all, b.sum_logprobs_all);
+    std::swap(j.sum_logprobs, b.sum_logprobs);
+    std::swap(j.avg_logprobs, b.avg_logprobs);
+    std::swap(j.entropy, b.entropy);
+    std::swap(j.score, b.score);
+    std::swap(j.seek_delta, b.seek_delta);
+    std::swap(j.has_ts, b.has_ts);
+    std::swap(j.failed, b.failed);
+    std::swap(j.completed, b.completed);
+    std::swap(j.step, b.step);
+}
+
 struct Sched {
+    int beam_k = 0;  // > 0: WHISPER_SAMPLING_BEAM_SEARCH with this many beams (t = 0 attempts)
+    std::vector<BeamJob> bj;
     Context* c;
     whisper_state* s;
     whisper_full_params p;
@@ -1908,6 +1969,11 @@ static bool logits_prepare(Sched& S, const std::vector<int>& act, bool want_nosp
 }
 static void logits_launch(Context* c, whisper_state* s, int n) {
     Workspace& w = s->ws;
+    if (s->beam_k > 0) {  // a beam step: top-k candidates per row (candidate 0 = the greedy record of the row)
+        KT kt(s, K_TOPK, (double)n * c->hp.n_vocab * 4);
+        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->beam_k, w.lrec, s->stream);
+        return;
+    }
     KT kt(s, K_LOGITS, (double)n * c->hp.n_vocab * 4);
     launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.tout, w.probs, w.lrec, s->stream);
 }
@@ -1915,6 +1981,12 @@ static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vect
     Context* c = S.c;
     Workspace& w = S.s->ws;
     hipStream_t st = S.s->stream;
+    if (S.s->beam_k > 0) {
+        WM_CHECK(hipMemcpyAsync(w.h_cand, w.cand, (size_t)n * kTopkMax * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        probs_rows.assign(n, {});
+        WM_CHECK(hipStreamSynchronize(st));
+        return;
+    }
     WM_CHECK(hipMemcpyAsync(w.h_tout, w.tout, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
     probs_rows.assign(n, {});
     if (any_probs) {  // sampling clips (t > 0): probs and logprobs rows for std::discrete_distribution
@@ -1956,6 +2028,7 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     const int n = P.n, pd = P.path == STEP_PDEC;
     P.pipe = par > 0;
     const int sig = dec_path_sig();
+    const int beam = s->beam_k | (s->split_slots ? 1 << 8 : 0);
     // read once: a setter stores its value before it bumps the generation, so a graph captured below under
     // generation `gen` holds that generation's (or a newer) stamps pointer and spin limit, and is retired later
     const int gen = g_pdec_gen.load(std::memory_order_acquire);
@@ -1971,9 +2044,9 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     }
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
-            g.par == par)
+            g.par == par && g.beam == beam)
             return &g;
-    whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, nullptr, {}};
+    whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
     hipGraph_t graph;
     s->capture_ev = &g.ev;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -2270,7 +2343,211 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
 // in flight measured 3720 vs 3201 audio-s/s back to back (profiles/r03_overlap_two_batches.txt),
 // where one 256-row decode step ran as two lockstep row groups before.
 static const int kPairMin = 128;
+// decoder rows (clips x beams) of a beam-search call with beam_size > 1: every live beam of every clip is a row of
+// one cache-form step (whisper_mi355x.h)
+static const int kBeamMaxRows = 32;
 std::atomic<long> g_decoded_tokens_total{0};
+
+// ---- beam search (WHISPER_SAMPLING_BEAM_SEARCH) --------------------------------------------------
+// The t = 0 attempt of every window decodes beam_k hypotheses per clip: one decoder row per live beam, the rows of
+// all clips in one step. A clip's rows share its cross slot and own their self slots (beam b of job k: slot
+// b * n_jobs + k, so beam 0 has the clip's own slot, the one the prefill writes). After a step the top-k kernel's
+// candidates are pooled per clip (beam.h), every live position takes its parent's state, runs process_step on
+// the new token as greedy decoding does, and the self-cache rows that differ are gathered (kernels/beam.hip).
+// beam_k = 1 takes greedy's own step plan (so it may run the persistent step and gives greedy's bits); beam_k > 1
+// takes the launch chain in the cache form, where a row's results do not depend on the step's other rows.
+static bool beam_attempt(const Sched& S, const Job& j) { return S.beam_k > 0 && j.temp_idx == 0 && S.temps[0] < 1e-6f; }
+
+static BeamCand to_cand(const TokOut& t) {
+    // (candidate 0 repeats the greedy record: id 0 with p 0 when the row has no token left)
+    return BeamCand{t.p > 0.0f ? t.id : -1, t.tid, t.p, t.plog, t.pt, t.ptsum};
+}
+
+// Contract points 4 / 5 for job k. rows: the beams whose candidates are cands[r * kTopkMax + rank] (`first`: the
+// prefill row, as beam 0); positions: the beam positions to fill. The copies of the re-parenting are appended
+// to `copies`.
+static void beam_reparent(Sched& S, int k, const std::vector<int>& rows, const TokOut* cands, const std::vector<int>& positions,
+                          bool first, std::vector<KvCopy>& copies) {
+    Job& j = S.jobs[k];
+    BeamJob& B = S.bj[k];
+    const int K = S.beam_k;
+    std::vector<BeamCand> bc(rows.size() * K);
+    std::vector<double> sums(rows.size());
+    for (size_t r = 0; r < rows.size(); r++) {
+        sums[r] = first ? 0.0 : B.beams[rows[r]].sum_logprobs_all;
+        for (int q = 0; q < K; q++) bc[r * K + q] = to_cand(cands[r * kTopkMax + q]);
+    }
+    const std::vector<BeamPick> picks = beam_select(rows, sums, bc.data(), K, positions);
+    std::vector<int> slots;
+    for (const Beam& b : B.beams) slots.push_back(b.sslot);
+    const std::vector<KvCopy> cp = beam_copies(picks, B.held, slots);
+    for (const KvCopy& x : cp) {
+        S.s->gather_rows += x.row1 - x.row0;
+        S.s->gather_rows_full += x.row1;
+    }
+    copies.insert(copies.end(), cp.begin(), cp.end());
+    const std::vector<Beam> old = B.beams;
+    for (const BeamPick& pk : picks) {
+        Beam& b = B.beams[pk.beam];
+        if (pk.parent < 0) { b.failed = true; continue; }
+        const int sl = b.sslot;
+        b = old[pk.parent];
+        b.sslot = sl;
+        if (!first) b.step++;
+        const size_t r = std::find(rows.begin(), rows.end(), pk.parent) - rows.begin();
+        swap_dec(j, b);
+        const bool more = process_step(S, j, cands[r * kTopkMax + pk.rank], nullptr);
+        swap_dec(j, b);
+        b.ended = !more;
+    }
+}
+
+// the self-cache copies of a step's re-parentings, all clips in one gather
+static void beam_gather(Sched& S, std::vector<KvCopy>& copies) {
+    if (copies.empty()) return;
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const Hparams& hp = c->hp;
+    const long upr = (long)hp.n_text_layer * 2 * hp.n_text_head * 8;  // 16-byte units of one row: layers, K | V, heads
+    const long need = beam_schedule(copies, upr);
+    if ((int)copies.size() > w.cap_jobs) WM_FAIL("beam search: %zu self-cache copies for %d slots", copies.size(), w.cap_jobs);
+    if (need > w.kvstage_units) {
+        WM_CHECK(hipStreamSynchronize(s->stream));
+        dfree(w.kvstage);
+        w.kvstage_units = 0;
+        dalloc(w.kvstage, (size_t)need * 16);
+        w.kvstage_units = need;
+    }
+    double rows = 0;
+    for (size_t i = 0; i < copies.size(); i++) {
+        w.h_kvcp[i] = copies[i];
+        rows += copies[i].row1 - copies[i].row0;
+    }
+    WM_CHECK(hipMemcpyAsync(w.kvcp, w.h_kvcp, copies.size() * sizeof(KvCopy), hipMemcpyHostToDevice, s->stream));
+    KT kt(s, K_KV_GATHER, rows * upr * 16 * 2);
+    launch_kv_gather(w.self, w.cap_jobs, hp.n_text_layer, hp.n_text_head, hp.n_text_ctx, w.h_kvcp, w.kvcp, (int)copies.size(),
+                     w.kvstage, w.kvstage_units, s->stream);
+}
+
+// Contract point 4: the beams of job k start from the candidates of its prefill row (rank r to beam r)
+static void beam_start(Sched& S, int k, const TokOut* cands, std::vector<KvCopy>& copies) {
+    Job& j = S.jobs[k];
+    BeamJob& B = S.bj[k];
+    const int K = S.beam_k, n_jobs = (int)S.jobs.size();
+    B.beams.assign(K, Beam());
+    B.held.assign(K, {});
+    B.held[0] = j.prompt;  // the prefill wrote the prompt's rows into the clip's own slot
+    std::vector<int> positions;
+    for (int b = 0; b < K; b++) {
+        B.beams[b].sslot = b * n_jobs + j.slot;
+        positions.push_back(b);
+    }
+    beam_reparent(S, k, {0}, cands, positions, true, copies);
+}
+
+// Contract point 6: score the beams, pick the winner, hand it to the Job and to attempt_done
+static void beam_finish(Sched& S, int k) {
+    Job& j = S.jobs[k];
+    BeamJob& B = S.bj[k];
+    const int K = S.beam_k;
+    std::vector<double> score(K);
+    std::vector<char> failed(K);
+    std::vector<whisper_state::BeamRec> recs(K);
+    for (int b = 0; b < K; b++) {
+        Beam& bm = B.beams[b];
+        for (const TokenData& t : bm.tokens) recs[b].tokens.push_back(t.id);
+        recs[b].sum_logprobs_all = bm.sum_logprobs_all;
+        if (!bm.failed) {  // as attempt_done scores a greedy attempt
+            swap_dec(j, bm);
+            j.tokens.resize(j.result_len);
+            score_seq(S.p, j);
+            if (j.result_len > 32 && j.entropy < S.p.entropy_thold) j.failed = true;
+            swap_dec(j, bm);
+        }
+        score[b] = bm.score;
+        failed[b] = bm.failed;
+        recs[b].flags = (bm.completed ? 1 : 0) | (bm.failed ? 2 : 0);
+    }
+    const int win = beam_winner(score, failed);
+    if (win >= 0) {
+        recs[win].flags |= 4;
+        swap_dec(j, B.beams[win]);
+    } else {
+        j.failed = true;
+    }
+    S.s->beam_info[k] = std::move(recs);
+    B.beams.clear();
+    attempt_done(S, j);
+}
+
+// One decode step of every live beam of the `bjobs` clips (all in PH_BEAM), then the re-parenting of each clip
+static void beam_step(Sched& S, const std::vector<int>& bjobs) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const int K = S.beam_k;
+    int* hi = w.h_ints;
+    std::vector<std::pair<int, int>> rows;  // {job, beam}
+    for (int k : bjobs) {
+        Job& j = S.jobs[k];
+        BeamJob& B = S.bj[k];
+        for (int b = 0; b < K; b++) {
+            Beam& bm = B.beams[b];
+            if (!bm.live()) continue;
+            const int r = (int)rows.size();
+            if (r >= w.cap_jobs) WM_FAIL("beam search: more than %d rows in a step", w.cap_jobs);
+            hi[r] = bm.tokens.back().id;
+            hi[w.cap_tok + r] = (int)j.prompt.size() + bm.step;
+            hi[2 * w.cap_tok + r] = j.slot;
+            hi[5 * w.cap_tok + r] = r;
+            w.h_sslot[r] = bm.sslot;
+            B.held[b].push_back(bm.tokens.back().id);  // this step writes the token's K/V row into the beam's slot
+            swap_dec(j, bm);
+            fill_ctl(S, j, w.h_ctl[r], false);
+            swap_dec(j, bm);
+            rows.push_back({k, b});
+        }
+    }
+    const int n = (int)rows.size();
+    struct Scope {  // the state's beam switches hold for this step only (also when an error unwinds)
+        whisper_state* s;
+        ~Scope() { s->beam_k = 0; s->split_slots = false; }
+    } scope{s};
+    s->beam_k = K;
+    s->split_slots = K > 1;
+    decoder_upload(c, s, n, n, false);
+    if (s->split_slots) WM_CHECK(hipMemcpyAsync(w.sslot, w.h_sslot, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, s->stream));
+    std::vector<std::vector<float>> probs_rows;
+    const double t_step = now_ms();
+    whisper_state::DecGraph* G = dec_graph(c, s, dec_path_prepare(c, s, n), 0);
+    if (!G->pdec) {
+        WM_CHECK(hipGraphLaunch(G->exec, s->stream));
+        logits_finish(S, n, false, probs_rows);
+        kt_flush_graph(s, *G);
+    } else {  // (beam_k = 1 only) as decode_step runs a persistent step
+        bool gave_up;
+        {
+            PdecRunLock lk(c->device);
+            WM_CHECK(hipGraphLaunch(G->exec, s->stream));
+            logits_finish(S, n, false, probs_rows);
+            gave_up = *s->ws.h_pd_err != 0;
+        }
+        kt_flush_graph(s, *G);
+        if (gave_up) rerun_given_up(S, n, false, probs_rows, t_step);
+    }
+    std::vector<KvCopy> copies;
+    for (int r0 = 0; r0 < n;) {
+        const int k = rows[r0].first;
+        std::vector<int> live;
+        int r1 = r0;
+        while (r1 < n && rows[r1].first == k) live.push_back(rows[r1++].second);
+        beam_reparent(S, k, live, w.h_cand + (size_t)r0 * kTopkMax, live, false, copies);
+        r0 = r1;
+    }
+    beam_gather(S, copies);
+}
 
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                           int n_jobs, bool on_device, const FullOpts& o, bool single_api);
@@ -2332,6 +2609,7 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
         s->lang_ids.push_back(t->lang_ids[j]);
         s->decisions.push_back(std::move(t->decisions[j]));
         s->align_info.push_back(t->align_info[j]);  // (its cost matrix stays in the twin's workspace)
+        s->beam_info.push_back(std::move(t->beam_info[j]));
     }
     s->align_ms = std::max(s->align_ms, t->align_ms);
     s->decoded_tokens += t->decoded_tokens;
@@ -2353,11 +2631,28 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                           int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
     WM_CHECK(hipSetDevice(c->device));
-    if (p.strategy != WHISPER_SAMPLING_GREEDY) {
-        fprintf(stderr, "whisper_mi355x: beam search is not implemented (the reference uses Greedy, whisper.rs:88)\n");
+    // beam search: beam_size hypotheses per clip at t = 0; patience is accepted and ignored
+    int beam_k = 0;
+    if (p.strategy == WHISPER_SAMPLING_BEAM_SEARCH) {
+        beam_k = std::max(1, p.beam_search.beam_size);
+        if (beam_k > kBeamMax) {
+            fprintf(stderr, "whisper_mi355x: beam_size %d > %d\n", beam_k, kBeamMax);
+            return -4;
+        }
+        if (o.fixed_tokens > 0) {
+            fprintf(stderr, "whisper_mi355x: the fixed-work mode decodes greedily (no beam search)\n");
+            return -1;
+        }
+        if (beam_k > 1 && (long)n_jobs * beam_k > kBeamMaxRows) {
+            fprintf(stderr, "whisper_mi355x: beam search of %d clips x %d beams exceeds %d decoder rows per step\n", n_jobs, beam_k,
+                    kBeamMaxRows);
+            return -1;
+        }
+    } else if (p.strategy != WHISPER_SAMPLING_GREEDY) {
+        fprintf(stderr, "whisper_mi355x: unknown sampling strategy %d\n", (int)p.strategy);
         return -100;
     }
-    if (p.greedy.best_of > 1) {
+    if (p.strategy == WHISPER_SAMPLING_GREEDY && p.greedy.best_of > 1) {
         // whisper.cpp uses best_of only for sampled (t > 0) fallback attempts: t = 0 is unaffected.
         // Sampled attempts here run one candidate per clip (the reference's Greedy{best_of: 1}).
         static bool warned = false;
@@ -2367,6 +2662,11 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     ensure_expanded(c, s->stream);  // quantized files: before anything is captured
     Sched S;
     S.c = c; S.s = s; S.p = p; S.o = o; S.single_api = single_api;
+    S.beam_k = beam_k;
+    S.bj.resize(beam_k > 0 ? n_jobs : 0);
+    s->beam_info.assign(n_jobs, {});
+    s->beam_k = 0;
+    s->split_slots = false;
     const Vocab& v = c->vocab;
     const Hparams& hp = c->hp;
     s->results.assign(n_jobs, {});
@@ -2376,8 +2676,9 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     s->align_ms = 0;
     s->decoded_tokens = 0;
     double t0 = now_ms();
-    s->direct = pick_direct(c, n_jobs);
-    ensure_ws(c, s, n_jobs);
+    // beams of one clip share its cross K/V cache slot: beam_k > 1 runs in the cache form, with a self slot per beam
+    s->direct = beam_k > 1 ? false : pick_direct(c, n_jobs);
+    ensure_ws(c, s, beam_k > 1 ? n_jobs * beam_k : n_jobs, n_jobs);
     compute_mel(c, s, pcm, n, n_jobs, on_device);
     S.t_mel = now_ms() - t0;
 
@@ -2534,13 +2835,33 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 }
                 decoder_forward(c, s, nt, (int)act.size());
                 run_logits(S, act, true, probs_rows);
+                bool any_beam = false;
+                for (int k : act) any_beam |= beam_attempt(S, S.jobs[k]);
+                if (any_beam) {  // the same rows again through the top-k form (candidate 0 = the record above)
+                    s->beam_k = S.beam_k;
+                    logits_launch(c, s, (int)act.size());
+                    std::vector<std::vector<float>> none;
+                    logits_finish(S, (int)act.size(), false, none);
+                    s->beam_k = 0;
+                }
                 S.t_prefill += now_ms() - tp;
                 copy_spot_logits(S, act);
+                std::vector<KvCopy> copies;
                 for (int r = 0; r < (int)act.size(); r++) {
                     Job& j = S.jobs[act[r]];
                     j.no_speech_prob = w.h_tout[r].nosp_prob;
+                    if (beam_attempt(S, j)) {
+                        beam_start(S, act[r], w.h_cand + (size_t)r * kTopkMax, copies);
+                        j.phase = PH_BEAM;
+                        continue;
+                    }
                     if (process_step(S, j, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) j.phase = PH_DECODE;
                     else attempt_done(S, j);
+                }
+                if (!copies.empty()) {  // the prompt's rows from every clip's own slot to its other beams' slots
+                    const double tg = now_ms();
+                    beam_gather(S, copies);
+                    S.t_decode += now_ms() - tg;
                 }
             }
         }
@@ -2567,6 +2888,24 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                     Job& j = S.jobs[act[r]];
                     if (!process_step(S, j, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) attempt_done(S, j);
                 }
+            }
+        }
+        // ---- beam search: one step for the live beams of every clip in a beam attempt; a clip without live
+        // beams ends its attempt (also right after the prefill)
+        {
+            std::vector<int> bjobs;
+            for (int k = 0; k < n_jobs; k++) {
+                if (S.jobs[k].phase != PH_BEAM) continue;
+                bool live = false;
+                for (const Beam& b : S.bj[k].beams) live |= b.live();
+                if (live) bjobs.push_back(k);
+                else beam_finish(S, k);
+            }
+            if (!bjobs.empty()) {
+                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
+                const double td = now_ms();
+                beam_step(S, bjobs);
+                S.t_decode += now_ms() - td;
             }
         }
         // ---- token timestamps: align every window that just finished with new segments

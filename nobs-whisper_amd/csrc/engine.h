@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/whisper_mi355x.h"
+#include "beam.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -186,6 +187,14 @@ struct Workspace {
     char* ring = nullptr;
     char* h_ring = nullptr;
     hipEvent_t ring_ev[2] = {nullptr, nullptr};
+    // beam search (engine.cpp beam_step): the self slot of every row of a step (rows of one clip share its cross
+    // slot in `slot`), the top-k candidates [cap_jobs][kTopkMax] of the logits rows, the self-cache copies of a
+    // re-parenting and the gather's staging buffer (grown on demand, 16-byte units)
+    int *sslot = nullptr, *h_sslot = nullptr;
+    TokOut *cand = nullptr, *h_cand = nullptr;
+    KvCopy *kvcp = nullptr, *h_kvcp = nullptr;
+    void* kvstage = nullptr;
+    long kvstage_units = 0;
     // mel / pcm
     float* pcm = nullptr;
     float* mel = nullptr;
@@ -216,7 +225,7 @@ struct Job;
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
-              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_NCLASS };
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 }  // namespace wm
@@ -266,7 +275,9 @@ struct whisper_state {
     // pdec: 0 = launch chain, 1 = the persistent step (kernels/pdec.hip)
     // (par: 0 for the per-step path; the pipelined path alternates two instances, 0 and 1, so that one step's
     // graph events are read while the other instance runs)
-    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; hipGraphExec_t exec; std::vector<KPending> ev; };
+    // (beam: 0 for greedy steps; a beam-search step's graph ends with the top-k kernel for beam_k candidates and,
+    // with split_slots, reads the rows' self slots from ws.sslot: beam_k | split_slots << 8)
+    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
     double cur_self_work = 0;                     // self-attention bytes of the current step
@@ -278,6 +289,16 @@ struct whisper_state {
     double pdec_lost_ms = 0;    // wall time of the given-up launches (wait until give-up + the re-run)
     double pdec_off_until = 0;  // now_ms() clock
     bool pdec_off = false;      // the backoff as frozen once per step (dec_path_prepare), so its plan, graph and step_variant agree
+    // beam search. beam_k > 0 while a beam step runs: its logits launch is the top-k form with beam_k candidates
+    // per row (results in ws.h_cand); split_slots: its rows' self slots differ from their cross slots (beam_k > 1:
+    // launch chain only, the persistent step has one slot array). beam_info[job] = the beams of the job's last
+    // beam-searched window (whisper_mi355x_beam_info).
+    int beam_k = 0;
+    bool split_slots = false;
+    struct BeamRec { std::vector<int> tokens; double sum_logprobs_all = 0; int flags = 0; };
+    std::vector<std::vector<BeamRec>> beam_info;
+    // cache rows the gather moved since the state was created, and what whole-sequence copies would have moved
+    double gather_rows = 0, gather_rows_full = 0;
 };
 
 struct whisper_context {

@@ -308,6 +308,21 @@ struct TokOut { int id, tid; float p, plog, pt, ptsum, nosp_prob, pad; };
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v,
                    TokOut* out, float* probs, void* rec, hipStream_t st);
 size_t logits_rec_bytes(int n_seq);
+// Top-k after the rules (beam search): the k <= kTopkMax most probable tokens of every row, p > 0, in
+// (p descending, id ascending) order, as TokOut records cand[row * kTopkMax + j]; j = 0 repeats the record
+// launch_logits returns for the row (same form by n_seq / rec, same bits: id 0, p 0 when no token has p > 0);
+// a record j > 0 without a token has id = -1. Rows are t = 0 rows (want_probs is ignored).
+constexpr int kTopkMax = 8;
+void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
+                        void* rec, hipStream_t st);
+// ---- self-cache gather (kernels/beam.hip; beam search re-parenting) --------------------------------
+// Every copy of the list (beam.h KvCopy, scheduled by beam_schedule) moves rows [row0, row1) of K and V of every
+// layer and head of the cache [n_slots][L][2][H][n_ctx][64] (2-byte type) from src_slot to dst_slot, as a
+// parallel assignment: one launch, and a second one when a copy goes through `stage` (stage_units 16-byte
+// units). copies_host is read for the bounds check and the grid, copies_dev by the kernel.
+struct KvCopy;
+void launch_kv_gather(void* cache, int n_slots, int L, int H, int n_ctx, const KvCopy* copies_host, const KvCopy* copies_dev,
+                      int n_copies, void* stage, long stage_units, hipStream_t st);
 // pipelined greedy decoding: advance every row's input token, position and SeqCtl on the device after a step
 // and copy its TokOut (+ the persistent launch's error word, if err) to a ring slot (kernels/logits.hip)
 void launch_decode_advance(int n, int ct, int beg, const TokOut* tout, int* ints, SeqCtl* ctl, TokOut* ring,

@@ -235,6 +235,172 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
     }
 }
 
+// logits_kernel for beam search (kernels.h launch_logits_topk): the same passes and expressions up to
+// the greedy record, which becomes candidate 0 (out[s * kTopkMax]); then candidate j = 1 .. topk - 1 is the block
+// argmax of the same float probs after the earlier winners were struck from the row (set to -inf), i.e. the
+// tokens with p > 0 in (p descending, id ascending) order. A text candidate carries the row's tid / pt / ptsum, a
+// timestamp candidate tid = id and pt = p (as the greedy record does); when fewer than topk tokens have p > 0
+// the remaining records have id = -1. (A copy, not a template flag: the greedy kernel's code stays as it was.)
+__global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
+                                                         VocabIds v, TokOut* __restrict__ out, int topk) {
+    const int s = blockIdx.x;
+    const SeqCtl c = ctl[s];
+    const float* L = logits + (long)s * ld;
+    const int n = v.n_vocab, tid = threadIdx.x;
+    __shared__ float shf[LT / 64];
+    __shared__ int shi[LT / 64];
+    __shared__ double shd[LT / 64];
+    __shared__ TokOut s_top[2];  // the greedy record; [1].tid / .pt: the row's tid / pt (a text candidate's)
+
+    extern __shared__ float s_row[];  // [NPT_LDS][LT]
+    RowSlice x{s_row};
+    // the register part first, then the LDS part in batches of 12 loads in flight (a load -> LDS
+    // store pair per element would wait out one memory latency per element)
+#pragma unroll
+    for (int k = NPT_LDS; k < NPT; k++) {
+        const int i = tid + k * LT;
+        x.set(k, i < n ? L[i] : -INFINITY);
+    }
+#pragma unroll
+    for (int k0 = 0; k0 < NPT_LDS; k0 += 12) {
+        float t[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            const int i = tid + (k0 + k) * LT;
+            t[k] = i < n ? L[i] : -INFINITY;
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) x.set(k0 + k, t[k]);
+    }
+    float nosp_prob = 0.0f;
+    if (c.want_nosp) {  // no-speech probability from the raw (unfiltered) logits
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < NPT; k++)
+            if (tid + k * LT < n) mx = fmaxf(mx, x.get(k));
+        mx = block_max(mx, shf);
+        float sm = 0.0f;
+#pragma unroll
+        for (int k = 0; k < NPT; k++)
+            if (tid + k * LT < n) sm += __expf(x.get(k) - mx);
+        sm = block_sum(sm, shf);
+        const float lse = logf(sm) + mx;
+        nosp_prob = expf(L[v.nosp] - lse);
+    }
+    // filtered logits, in place
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int i = tid + k * LT;
+        if (i < n) x.set(k, masked_logit(x.get(k), i, c, v));
+    }
+    // log-softmax of the filtered logits
+    float mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
+    mx = block_max(mx, shf);
+    float sm = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NPT; k++)
+        if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
+    sm = block_sum(sm, shf);
+    const float lse = logf(sm) + mx;
+    // timestamp rule
+    float mts = -INFINITY, mtext = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int i = tid + k * LT;
+        const float lp = x.get(k) > -INFINITY ? x.get(k) - lse : -INFINITY;
+        if (i >= v.beg) mts = fmaxf(mts, lp); else mtext = fmaxf(mtext, lp);
+    }
+    mts = block_max(mts, shf);
+    mtext = block_max(mtext, shf);
+    float sts = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int i = tid + k * LT;
+        if (i < v.beg) continue;
+        const float lp = x.get(k) > -INFINITY ? x.get(k) - lse : -INFINITY;
+        if (lp > -INFINITY) sts += expf(lp - mts);  // libm-accurate: this sum decides the timestamp rule
+    }
+    sts = block_sum(sts, shf);
+    const float ts_logprob = sts > 0.0f ? logf(sts) + mts : -INFINITY;
+    const bool mask_text = ts_logprob > mtext;
+    // probs, argmax (all) and argmax / sum over timestamps
+    float best = 0.0f, best_ts = 0.0f;
+    int ibest = 0x7fffffff, its = 0x7fffffff;
+    double sum_ts = 0.0;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int i = tid + k * LT;
+        if (i >= n) continue;
+        float xv = x.get(k);
+        if (mask_text && i < v.beg) xv = -INFINITY;
+        const float p = xv == -INFINITY ? 0.0f : __expf(xv - lse);
+        if (p > best) { best = p; ibest = i; }
+        if (i >= v.beg) {
+            sum_ts += (double)p;
+            if (p > best_ts) { best_ts = p; its = i; }
+        }
+    }
+    block_argmax(best, ibest, shf, shi);
+    block_argmax(best_ts, its, shf, shi);
+    sum_ts = block_sum_d(sum_ts, shd);
+    if (tid == 0) {
+        TokOut r;
+        r.id = best > 0.0f ? ibest : 0;
+        r.p = best;
+        {
+            float xv = masked_logit(L[r.id], r.id, c, v);
+            if (mask_text && r.id < v.beg) xv = -INFINITY;
+            r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
+        }
+        r.tid = best_ts > 0.0f ? its : 0;
+        r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
+        r.ptsum = (float)sum_ts;
+        s_top[1].tid = r.tid;
+        s_top[1].pt = r.pt;
+        if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
+        r.nosp_prob = nosp_prob;
+        r.pad = 0.0f;
+        out[(long)s * kTopkMax] = r;
+        s_top[0] = r;
+    }
+    // best / ibest are the block's in every thread: each round strikes the last winner from the row
+    for (int j = 1; j < topk; j++) {
+        const bool dead = !(best > 0.0f);  // no token with p > 0 is left (uniform)
+        float bj = 0.0f;
+        int ij = 0x7fffffff;
+        if (!dead) {
+#pragma unroll
+            for (int k = 0; k < NPT; k++) {
+                const int i = tid + k * LT;
+                if (i == ibest) x.set(k, -INFINITY);
+                if (i >= n) continue;
+                float xv = x.get(k);
+                if (mask_text && i < v.beg) xv = -INFINITY;
+                const float p = xv == -INFINITY ? 0.0f : __expf(xv - lse);
+                if (p > bj) { bj = p; ij = i; }
+            }
+        }
+        block_argmax(bj, ij, shf, shi);  // (its first barrier also orders s_top against thread 0's reads below)
+        if (tid == 0) {
+            TokOut r = s_top[0];
+            if (!(bj > 0.0f)) {
+                r.id = -1; r.tid = 0; r.p = 0.0f; r.plog = -INFINITY; r.pt = 0.0f;
+            } else {
+                r.id = ij;
+                r.p = bj;
+                r.plog = masked_logit(L[ij], ij, c, v) - lse;  // p > 0: the filtered logit is finite
+                if (ij >= v.beg) { r.tid = ij; r.pt = bj; }
+                else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
+            }
+            out[(long)s * kTopkMax + j] = r;
+        }
+        best = bj;
+        ibest = ij;
+    }
+}
+
 // ---- split form for few rows (decode steps of <= 16 clips: one 1024-thread workgroup per row leaves
 // the chip idle and took 38 us per step at one clip) -------------------------------------------------
 // Pass 1: KS workgroups per row, each over a chunk of the vocabulary, write per-chunk statistics of
@@ -414,6 +580,130 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
     }
 }
 
+// The split form's pass 2 for top-k rows (beam search): thread 0 combines the chunk records exactly as
+// logits_combine_kernel does (the same expressions in the same order, so candidate 0 is that kernel's record
+// bit for bit), while the 1024 threads hold the filtered row in LDS / registers as logits_kernel does. Candidate
+// j > 0 is the block argmax of the filtered logits x (lowest index on ties; text tokens excluded when the
+// timestamp rule fired) without the earlier winners, with p = e^(x - lse), plog = x - lse: the split form's own
+// key (it orders by x where the one-workgroup form orders by the rounded p). A candidate whose p underflows
+// to 0, and every one after it, has id = -1.
+__global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __restrict__ logits, long ld,
+                                                                 const SeqCtl* __restrict__ ctl, VocabIds v,
+                                                                 const LogitRec* __restrict__ rec, TokOut* __restrict__ cand,
+                                                                 int topk) {
+    const int s = blockIdx.x, tid = threadIdx.x, n = v.n_vocab;
+    const SeqCtl q = ctl[s];
+    const float* L = logits + (long)s * ld;
+    __shared__ float shf[LT / 64];
+    __shared__ int shi[LT / 64];
+    __shared__ float sh_lse;
+    __shared__ int sh_mask;
+    __shared__ TokOut s_top[2];  // candidate 0; [1].tid / .pt: the row's tid / pt (a text candidate's)
+    __shared__ int sh_win;       // the last winner (-1: no token with p > 0 is left)
+    extern __shared__ float s_row[];  // [NPT_LDS][LT]
+    RowSlice x{s_row};
+#pragma unroll
+    for (int k = NPT_LDS; k < NPT; k++) {
+        const int i = tid + k * LT;
+        x.set(k, i < n ? masked_logit(L[i], i, q, v) : -INFINITY);
+    }
+#pragma unroll
+    for (int k0 = 0; k0 < NPT_LDS; k0 += 12) {
+        float t[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            const int i = tid + (k0 + k) * LT;
+            t[k] = i < n ? L[i] : -INFINITY;
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            const int i = tid + (k0 + k) * LT;
+            x.set(k0 + k, i < n ? masked_logit(t[k], i, q, v) : -INFINITY);
+        }
+    }
+    if (tid == 0) {
+        const LogitRec* R = rec + (long)s * KS;
+        float M = -INFINITY, Mts = -INFINITY, Mtx = -INFINITY, Mr = -INFINITY;
+        int ix = 0x7fffffff, its = 0x7fffffff;
+        for (int c = 0; c < KS; c++) {
+            argmax_pair(M, ix, R[c].m, R[c].ix_all);
+            argmax_pair(Mts, its, R[c].m_ts, R[c].ix_ts);
+            Mtx = fmaxf(Mtx, R[c].m_text);
+            Mr = fmaxf(Mr, R[c].m_r);
+        }
+        float S = 0.0f, Sts = 0.0f, Sr = 0.0f;
+        for (int c = 0; c < KS; c++) {
+            if (R[c].m > -INFINITY) S += R[c].s * expf(R[c].m - M);
+            if (R[c].m_ts > -INFINITY) Sts += R[c].s_ts * expf(R[c].m_ts - Mts);
+            if (q.want_nosp && R[c].m_r > -INFINITY) Sr += R[c].s_r * expf(R[c].m_r - Mr);
+        }
+        const float lse = logf(S) + M;
+        const float mts = Mts - lse, mtext = Mtx - lse;
+        const float ts_logprob = Sts > 0.0f ? logf(Sts) + mts : -INFINITY;
+        const bool mask_text = ts_logprob > mtext;
+        TokOut r;
+        const float xb = mask_text ? Mts : M;
+        const int ib = mask_text ? its : ix;
+        const float best = xb > -INFINITY ? __expf(xb - lse) : 0.0f;
+        r.id = best > 0.0f ? ib : 0;
+        r.p = best;
+        {
+            float xv = masked_logit(L[r.id], r.id, q, v);
+            if (mask_text && r.id < v.beg) xv = -INFINITY;
+            r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
+        }
+        const float best_ts = Mts > -INFINITY ? __expf(Mts - lse) : 0.0f;
+        const double sum_ts = Mts > -INFINITY ? (double)Sts * (double)expf(Mts - lse) : 0.0;
+        r.tid = best_ts > 0.0f ? its : 0;
+        r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
+        r.ptsum = (float)sum_ts;
+        s_top[1].tid = r.tid;
+        s_top[1].pt = r.pt;
+        if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
+        r.nosp_prob = q.want_nosp ? expf(L[v.nosp] - (logf(Sr) + Mr)) : 0.0f;
+        r.pad = 0.0f;
+        cand[(long)s * kTopkMax] = r;
+        s_top[0] = r;
+        sh_win = best > 0.0f ? ib : -1;
+        sh_lse = lse;
+        sh_mask = mask_text;
+    }
+    __syncthreads();
+    const float lse = sh_lse;
+    const bool mask_text = sh_mask;
+    int win = sh_win;
+    for (int j = 1; j < topk; j++) {
+        float bj = -INFINITY;
+        int ij = 0x7fffffff;
+        if (win >= 0) {
+#pragma unroll
+            for (int k = 0; k < NPT; k++) {
+                const int i = tid + k * LT;
+                if (i == win) x.set(k, -INFINITY);
+                const float xv = x.get(k);
+                if (i >= n || (mask_text && i < v.beg)) continue;
+                if (xv > bj) { bj = xv; ij = i; }
+            }
+        }
+        block_argmax(bj, ij, shf, shi);
+        const float p = bj > -INFINITY ? __expf(bj - lse) : 0.0f;
+        if (tid == 0) {
+            TokOut r = s_top[0];
+            if (!(p > 0.0f)) {
+                r.id = -1; r.tid = 0; r.p = 0.0f; r.plog = -INFINITY; r.pt = 0.0f;
+            } else {
+                r.id = ij;
+                r.p = p;
+                r.plog = bj - lse;
+                if (ij >= v.beg) { r.tid = ij; r.pt = p; }
+                else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
+            }
+            cand[(long)s * kTopkMax + j] = r;
+        }
+        win = p > 0.0f ? ij : -1;
+    }
+}
+
 // rows up to this count take the split form (16 chunk workgroups per row + a combine)
 static const int kLogitsSplitMax = 16;
 
@@ -427,6 +717,22 @@ void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, c
         return;
     }
     logits_kernel<<<n_seq, LT, (size_t)NPT_LDS * LT * sizeof(float), st>>>(logits, ld, ctl, v, out, probs);
+}
+
+// Top-k after the rules: the form is chosen exactly as launch_logits chooses it for the same n_seq / rec, so
+// candidate 0 of a row is the TokOut launch_logits would return for it.
+void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
+                        void* rec, hipStream_t st) {
+    if (n_seq <= 0) return;
+    if (k < 1 || k > kTopkMax) WM_FAIL("top-k %d outside 1..%d", k, kTopkMax);
+    if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
+    const size_t lds = (size_t)NPT_LDS * LT * sizeof(float);
+    if (rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
+        logits_part_kernel<<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec);
+        logits_topk_combine_kernel<<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, cand, k);
+        return;
+    }
+    logits_topk_kernel<<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k);
 }
 
 // ---- device-side step advance (pipelined greedy decoding, engine.cpp decode_pipelined) -----------------------

@@ -55,6 +55,14 @@ PdecGranules pdec_granules(int d, int L, int H) {
 // 2-4 clips) workgroups take several.
 int pdec_cross_splits(int H, int rows) { return std::max(1, std::min({kG / H, rows / 16, 8})); }
 
+// Zeroes the hand-off block before every launch (gr.bytes is a multiple of 16). A kernel, not hipMemsetAsync: as a
+// memset node of a captured step, replayed on the HIP runtime that PyTorch bundles, the memset left the block's
+// last few hundred bytes (the error word and the zero page) as they were; on memory recycled from a freed buffer
+// the error word then held stale data and every step of the state was read as a give-up.
+__global__ void __launch_bounds__(kNT) pdec_zero_kernel(uint4* __restrict__ p, long n) {
+    for (long i = (long)blockIdx.x * kNT + threadIdx.x; i < n; i += (long)gridDim.x * kNT) p[i] = make_uint4(0, 0, 0, 0);
+}
+
 void launch_pdec(DType dt, const PdecArgs& a, hipStream_t st) {
     if (a.M < 1 || a.M > kPdecMaxRows) WM_FAIL("pdec: %d rows", a.M);
     if ((long)a.M * (a.d / 64) * a.s_cross * 66 > a.gr.err_bytes / 8 - a.gr.part) WM_FAIL("pdec: split count");
@@ -64,7 +72,7 @@ void launch_pdec(DType dt, const PdecArgs& a, hipStream_t st) {
     const PdecLds ll = pdec_lds(a.d, a.M, a.s_cross);
     if (ll.bytes > 160 * 1024) WM_FAIL("pdec: %d bytes of LDS", ll.bytes);
     const size_t lds = ll.bytes;
-    WM_CHECK(hipMemsetAsync(a.sync, 0, a.gr.bytes, st));
+    pdec_zero_kernel<<<64, kNT, 0, st>>>((uint4*)a.sync, a.gr.bytes / 16);
     const bool one = a.M == 1;  // the one-row build (the app's one clip per call)
     if (a.quant) {
         if (dt != DType::F16) WM_FAIL("pdec: GGML blocks with a bf16 context");

@@ -31,8 +31,8 @@
 // needs with sc1 loads (16 in flight per thread in the wide sweeps) until every tag equals the phase's tag
 // (layer * 8 + phase + 1), then uses the data bits. x rows travel as f32 granules, everything rounded to T
 // (q/k/v, attention outputs, cross-Q, GELU rows) as packed T pairs; a cross-attention split publishes its
-// partial {o[64], max, sum} as 66 granules that split 0's workgroup gathers. The block is zeroed by a memset
-// node before every launch, and a buffer is reused by the next layer (safe: every layer's phase A reads all
+// partial {o[64], max, sum} as 66 granules that split 0's workgroup gathers. The block is zeroed by a kernel
+// (pdec.hip) before every launch, and a buffer is reused by the next layer (safe: every layer's phase A reads all
 // of x0, i.e. waits for every workgroup's last phase of the layer before).
 // Bounded waits: a wait gives up after spin_ticks of s_memrealtime (100 MHz; 50 ms by default), sets the
 // error word and the workgroup exits; every other wait sees the error word and exits too, so the grid always
@@ -389,7 +389,7 @@ __device__ __forceinline__ void ln_rows(const float* xf, int M, const float* gam
 // Every handed-off value travels as ONE naturally aligned 8-byte granule {tag, 32 bits of data} written by
 // ONE sc1 store: the data is the flag, so a producer neither drains nor signals, and a consumer re-reads
 // the granules it needs (sc1 loads) until every tag equals the phase's tag = layer * 8 + phase + 1 (never 0).
-// The block is zeroed by a memset node before every launch. A buffer is reused by the next layer: safe
+// The block is zeroed by a kernel (pdec.hip) before every launch. A buffer is reused by the next layer: safe
 // because every layer's phase A reads all of x0, i.e. waits for every workgroup's last phase of the layer
 // before, and every buffer of layer l + 1 is written after some workgroup's phase A of layer l + 1.
 typedef __attribute__((address_space(1))) unsigned long long gu64;

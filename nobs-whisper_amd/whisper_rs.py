@@ -106,6 +106,14 @@ class WindowDecision(C.Structure):
                 ("entropy0", C.c_float), ("no_speech_prob", C.c_float), ("pad", C.c_float)]
 
 
+class Cand(C.Structure):
+    """struct whisper_mi355x_cand (include/whisper_mi355x.h): one candidate of the top-k logits kernel."""
+    _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("plog", C.c_float), ("pt", C.c_float),
+                ("ptsum", C.c_float), ("no_speech_prob", C.c_float), ("pad", C.c_float)]
+
+
+BEAM_COMPLETED, BEAM_FAILED, BEAM_WINNER = 1, 2, 4
+
 _lib = None
 
 
@@ -157,6 +165,10 @@ def lib() -> C.CDLL:
         "whisper_mi355x_full_batch": (C.c_int, [vp, vp, FullParams, C.POINTER(vp), ip, C.c_int, C.c_bool, C.c_int]),
         "whisper_mi355x_full_batch_forced": (C.c_int, [vp, vp, FullParams, C.POINTER(vp), ip, C.c_int, C.c_bool, C.c_int,
                                                        ip, ip, C.c_int, C.POINTER(C.c_float)]),
+        "whisper_mi355x_beam_info": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(C.c_double), ip]),
+        "whisper_mi355x_debug_logits_topk": (C.c_int, [vp, vp, C.c_int, ip, fp, C.c_int, C.c_int, C.POINTER(Cand),
+                                                       C.POINTER(Cand)]),
+        "whisper_mi355x_debug_kv_gather": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip]),
         "whisper_mi355x_batch_n_segments": (C.c_int, [vp, C.c_int]),
         "whisper_mi355x_batch_segment_text": (C.c_char_p, [vp, C.c_int, C.c_int]),
         "whisper_mi355x_batch_segment_t0": (C.c_int64, [vp, C.c_int, C.c_int]),
@@ -233,6 +245,18 @@ def reference_full_params(language: str | None = "en", initial_prompt: str | Non
     p.no_speech_thold = 0.6
     p.entropy_thold = 2.4
     p.logprob_thold = -1.0
+    return p
+
+
+def beam_full_params(beam_size: int = 5, language: str | None = "en", initial_prompt: str | None = None,
+                     patience: float = -1.0) -> FullParams:
+    """FullParams::new(BeamSearch{beam_size, patience}) + the same setters as reference_full_params."""
+    p = reference_full_params(language, initial_prompt)
+    d = lib().whisper_full_default_params(BEAM_SEARCH)
+    p.strategy = BEAM_SEARCH
+    p.greedy.best_of = d.greedy.best_of
+    p.beam_search.beam_size = beam_size
+    p.beam_search.patience = patience
     return p
 
 
@@ -389,6 +413,22 @@ class WhisperState:
                                L.whisper_mi355x_batch_segment_t1(self.ptr, job, i),
                                L.whisper_mi355x_batch_segment_text(self.ptr, job, i), toks))
         return out
+
+    def beam_info(self, job: int = 0) -> list:
+        """whisper_mi355x_beam_info: the beams of the job's last beam-searched window, as dicts {tokens,
+        sum_logprobs_all, completed, failed, winner}; [] when there is none."""
+        out = []
+        ip_ = C.POINTER(C.c_int)
+        while True:
+            cap = 512
+            toks = (C.c_int * cap)()
+            sm = C.c_double(0)
+            fl = C.c_int(0)
+            n = self.L.whisper_mi355x_beam_info(self.ptr, job, len(out), C.cast(toks, ip_), cap, C.byref(sm), C.byref(fl))
+            if n < 0:
+                return out
+            out.append(dict(tokens=list(toks[:n]), sum_logprobs_all=sm.value, completed=bool(fl.value & BEAM_COMPLETED),
+                            failed=bool(fl.value & BEAM_FAILED), winner=bool(fl.value & BEAM_WINNER)))
 
     def decisions(self, job: int = 0) -> list:
         """Per-window temperature-fallback decisions of the last full (job 0) / full_batch call."""

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 import struct
 
 import numpy as np
@@ -367,9 +368,11 @@ def write_model(path: str, shape: str = "tiny", seed: int = 0, ftype: int = 1, q
     for q in GGML_TYPES:
         if shape.endswith("+" + q):
             shape, qtype = shape[:-len(q) - 1], q
-    eot = shape.endswith("+eot")
+    m = re.search(r"\+eot(\d*)$", shape)  # "+eot": CONF_EOT_BOOST; "+eot24": that boost (EOT wins more often)
+    eot = m is not None
+    eot_boost = float(m.group(1)) if eot and m.group(1) else CONF_EOT_BOOST
     if eot:
-        shape = shape[:-4]
+        shape = shape[:m.start()]
     conf = shape.endswith("+conf")
     n_vocab, n_mels, d, h, n_enc, n_dec = SHAPES[shape[:-5] if conf else shape]
     rng = np.random.default_rng(seed)
@@ -394,7 +397,7 @@ def write_model(path: str, shape: str = "tiny", seed: int = 0, ftype: int = 1, q
                 progress(name)
             data = init_tensor(rng, name, shp, d, n_mels)
             if conf:
-                data = conf_adjust(name, data, n_vocab, CONF_EOT_BOOST if eot else 0.0)
+                data = conf_adjust(name, data, n_vocab, eot_boost if eot else 0.0)
             use_f16 = (ftype == 1) and not is_f32
             quant = qtype is not None and len(shp) == 2 and name not in QUANT_SKIP
             nb = name.encode()
