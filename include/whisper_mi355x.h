@@ -283,6 +283,32 @@ WHISPER_API int whisper_mi355x_debug_logits_topk(struct whisper_context * ctx, c
 WHISPER_API int whisper_mi355x_debug_kv_gather(struct whisper_context * ctx, void * cache, int n_slots, int L, int H,
                                                int n_ctx, const int * copies, int n_copies, int * n_staged);
 
+/* Debug: the greedy logits kernels and the device-side step advance (kernels/logits.hip) on caller data, one
+ * launch each through the engine's launcher.
+ * logits: logits = n device rows [n][n_vocab] (f32, the context's vocabulary); ctl = host [n], the per-row rule
+ * inputs (every field per row, rows may differ); form = 0: one workgroup per row, 1: the form the engine takes for
+ * this row count (the split form up to 16 rows, one workgroup per row above). out = host [n] records. probs = host
+ * [n][2][n_vocab] (probs | logprobs per row) or NULL; required when a row has want_probs. Rows without want_probs
+ * are not written by the kernels: their probs rows come back as NaN (all bits set).
+ * decode_advance: n rows of a step with ct >= n entries per region; tout = host [n] (the step's records), ints =
+ * host [5 ct] (tok | pos | slot | nkv_self | nkv_cross), ctl = host [ct], ring = host [ct], all three read and
+ * written back (entries the kernel does not own return as given); err = host error word or NULL; *ring_err is
+ * uploaded as given and receives the ring's copy of the word (0 when err is NULL).
+ * Return 0, -1 on bad arguments (nothing touches the device), or the runtime error code. */
+struct whisper_mi355x_seq_ctl {
+    int32_t is_initial, last_ts, penult_ts, has_ts, seek_delta;
+    float   temperature;
+    int32_t suppress_blank, no_timestamps, suppress_eot, tid0_initial; /* tid0_initial < 0: no max_initial_ts rule */
+    int32_t want_probs, want_nosp;
+};
+WHISPER_API int whisper_mi355x_debug_logits(struct whisper_context * ctx, const float * logits, int n,
+                                            const struct whisper_mi355x_seq_ctl * ctl, int form,
+                                            struct whisper_mi355x_cand * out, float * probs);
+WHISPER_API int whisper_mi355x_debug_decode_advance(struct whisper_context * ctx, int n, int ct, int beg,
+                                                    const struct whisper_mi355x_cand * tout, int * ints,
+                                                    struct whisper_mi355x_seq_ctl * ctl, const unsigned * err,
+                                                    struct whisper_mi355x_cand * ring, unsigned * ring_err);
+
 /* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
  * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.
  * scores: q [n_text_layer][sum n_rows][d] (device, compute type: the cross-Q rows of every layer, already scaled

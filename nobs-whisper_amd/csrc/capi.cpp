@@ -951,6 +951,65 @@ int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* l
         return 0;
     });
 }
+// ---- the greedy logits kernels and the step advance on caller data (kernels/logits.hip) --------------------------
+static_assert(sizeof(whisper_mi355x_seq_ctl) == sizeof(SeqCtl), "whisper_mi355x_seq_ctl mirrors SeqCtl");
+int whisper_mi355x_debug_logits(struct whisper_context* ctx, const float* logits, int n,
+                                const struct whisper_mi355x_seq_ctl* ctl, int form, struct whisper_mi355x_cand* out,
+                                float* probs) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !logits || !ctl || !out || n <= 0 || form < 0 || form > 1) return -1;
+        for (int r = 0; r < n; r++)
+            if (ctl[r].want_probs && !probs) return -1;
+        hipSetDevice(ctx->c.device);
+        const int V = ctx->c.hp.n_vocab;
+        const size_t pbytes = (size_t)n * 2 * V * sizeof(float);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        SeqCtl* d_ctl = (SeqCtl*)b.get(n * sizeof(SeqCtl));
+        TokOut* d_out = (TokOut*)b.get(n * sizeof(TokOut));
+        float* d_probs = probs ? (float*)b.get(pbytes) : nullptr;
+        void* rec = form ? b.get(logits_rec_bytes(n)) : nullptr;
+        WM_CHECK(hipMemcpyAsync(d_ctl, ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
+        if (d_probs) WM_CHECK(hipMemsetAsync(d_probs, 0xff, pbytes, st));  // rows the kernel leaves alone read as NaN
+        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out, d_probs, rec, st);
+        WM_CHECK(hipGetLastError());
+        WM_CHECK(hipMemcpyAsync(out, d_out, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        if (d_probs) WM_CHECK(hipMemcpyAsync(probs, d_probs, pbytes, hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+int whisper_mi355x_debug_decode_advance(struct whisper_context* ctx, int n, int ct, int beg,
+                                        const struct whisper_mi355x_cand* tout, int* ints,
+                                        struct whisper_mi355x_seq_ctl* ctl, const unsigned* err,
+                                        struct whisper_mi355x_cand* ring, unsigned* ring_err) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !tout || !ints || !ctl || !ring || !ring_err || n <= 0 || ct < n) return -1;
+        hipSetDevice(ctx->c.device);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        TokOut* d_tout = (TokOut*)b.get(n * sizeof(TokOut));
+        int* d_ints = (int*)b.get((size_t)5 * ct * sizeof(int));
+        SeqCtl* d_ctl = (SeqCtl*)b.get(ct * sizeof(SeqCtl));
+        TokOut* d_ring = (TokOut*)b.get(ct * sizeof(TokOut));
+        unsigned* d_err = (unsigned*)b.get(2 * sizeof(unsigned));  // [0]: the error word, [1]: the ring's copy
+        const unsigned h_err[2] = {err ? *err : 0u, *ring_err};
+        WM_CHECK(hipMemcpyAsync(d_tout, tout, n * sizeof(TokOut), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_ints, ints, (size_t)5 * ct * sizeof(int), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_ctl, ctl, ct * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_ring, ring, ct * sizeof(TokOut), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_err, h_err, sizeof(h_err), hipMemcpyHostToDevice, st));
+        launch_decode_advance(n, ct, beg, d_tout, d_ints, d_ctl, d_ring, err ? d_err : nullptr, d_err + 1, st);
+        WM_CHECK(hipMemcpyAsync(ints, d_ints, (size_t)5 * ct * sizeof(int), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipMemcpyAsync(ctl, d_ctl, ct * sizeof(SeqCtl), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipMemcpyAsync(ring, d_ring, ct * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipMemcpyAsync(ring_err, d_err + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
 int whisper_mi355x_debug_kv_gather(struct whisper_context* ctx, void* cache, int n_slots, int L, int H, int n_ctx,
                                    const int* copies, int n_copies, int* n_staged) {
     return guarded(nullptr, [&]() -> int {

@@ -112,6 +112,14 @@ class Cand(C.Structure):
                 ("ptsum", C.c_float), ("no_speech_prob", C.c_float), ("pad", C.c_float)]
 
 
+class SeqCtl(C.Structure):
+    """struct whisper_mi355x_seq_ctl (include/whisper_mi355x.h): one row's rule inputs of the logits kernels."""
+    _fields_ = [("is_initial", C.c_int32), ("last_ts", C.c_int32), ("penult_ts", C.c_int32), ("has_ts", C.c_int32),
+                ("seek_delta", C.c_int32), ("temperature", C.c_float), ("suppress_blank", C.c_int32),
+                ("no_timestamps", C.c_int32), ("suppress_eot", C.c_int32), ("tid0_initial", C.c_int32),
+                ("want_probs", C.c_int32), ("want_nosp", C.c_int32)]
+
+
 BEAM_COMPLETED, BEAM_FAILED, BEAM_WINNER = 1, 2, 4
 
 _lib = None
@@ -169,6 +177,10 @@ def lib() -> C.CDLL:
         "whisper_mi355x_debug_logits_topk": (C.c_int, [vp, vp, C.c_int, ip, fp, C.c_int, C.c_int, C.POINTER(Cand),
                                                        C.POINTER(Cand)]),
         "whisper_mi355x_debug_kv_gather": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip]),
+        "whisper_mi355x_debug_logits": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, C.POINTER(Cand), fp]),
+        "whisper_mi355x_debug_decode_advance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Cand), ip,
+                                                          C.POINTER(SeqCtl), C.POINTER(C.c_uint), C.POINTER(Cand),
+                                                          C.POINTER(C.c_uint)]),
         "whisper_mi355x_batch_n_segments": (C.c_int, [vp, C.c_int]),
         "whisper_mi355x_batch_segment_text": (C.c_char_p, [vp, C.c_int, C.c_int]),
         "whisper_mi355x_batch_segment_t0": (C.c_int64, [vp, C.c_int, C.c_int]),

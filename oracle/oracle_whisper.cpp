@@ -1024,5 +1024,22 @@ int oracle_decoder_tokens(void* sp, int* out, int cap) {
     for (int i = 0; i < n; i++) out[i] = t[i].id;
     return (int)t.size();
 }
+// process_logits + sample_token(best) on caller data (tests/logits_ref.py is checked against it): row [n_vocab],
+// the ids generated so far, the decoder's has_ts / seek_delta -> logprobs, probs [n_vocab] and the greedy
+// TokenData (out[6]: id, tid as ints; p, plog, pt, ptsum as floats)
+void oracle_process_logits(void* mp, const float* row, const int* toks, int n_toks, int has_ts, int seek_delta,
+                           const OracleParams* p, float temperature, float* logprobs, float* probs, void* out) {
+    Model& m = *(Model*)mp;
+    State s;
+    Decoder dec;
+    for (int i = 0; i < n_toks; i++) dec.sequence.tokens.push_back(TokenData{toks[i], 0, 0.0f, 0.0f, 0.0f, 0.0f});
+    dec.has_ts = has_ts != 0;
+    dec.seek_delta = seek_delta;
+    process_logits(m, s, dec, *p, temperature, row);
+    const TokenData td = sample_token(m, s, dec, true);
+    std::copy(dec.logprobs.begin(), dec.logprobs.end(), logprobs);
+    std::copy(dec.probs.begin(), dec.probs.end(), probs);
+    memcpy(out, &td, sizeof(td));
+}
 
 }  // extern "C"

@@ -26,6 +26,12 @@ def decisions_to_dicts(arr) -> list:
     return [{f: getattr(d, f) for f, _ in Decision._fields_ if f != "pad"} for d in arr]
 
 
+class TokenData(C.Structure):
+    """oracle_whisper.cpp's TokenData."""
+    _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("plog", C.c_float), ("pt", C.c_float),
+                ("ptsum", C.c_float)]
+
+
 class OracleParams(C.Structure):
     _fields_ = [
         ("language", C.c_char_p), ("initial_prompt", C.c_char_p),
@@ -103,6 +109,8 @@ def lib():
             "oracle_segment_seek": (C.c_int, [vp, C.c_int]),
             "oracle_step_logits": (C.c_long, [vp, vp, fp, C.c_long]),
             "oracle_decoder_tokens": (C.c_int, [vp, ip, C.c_int]),
+            "oracle_process_logits": (None, [vp, fp, ip, C.c_int, C.c_int, C.c_int, C.POINTER(OracleParams), C.c_float,
+                                             fp, fp, vp]),
             "oracle_mel_tables": (None, [fp, fp, fp]),
             "oracle_tensor": (C.c_long, [vp, C.c_char_p, C.c_int, fp, C.c_long]),
             "oracle_calculate_rms": (C.c_float, [fp, C.c_int]),
@@ -212,6 +220,18 @@ class Oracle:
 
     def token_str(self, i: int) -> bytes:
         return self.L.oracle_token_str(self.m, i)
+
+    def process_logits(self, row, tokens, has_ts: bool, seek_delta: int, params: OracleParams, temperature: float):
+        """process_logits + sample_token(best) for the row that follows the generated ids `tokens`:
+        (logprobs [V] f32, probs [V] f32, the greedy TokenData as a dict)."""
+        row = np.ascontiguousarray(row, dtype=np.float32)
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        lp = np.empty(self.n_vocab, np.float32)
+        pr = np.empty(self.n_vocab, np.float32)
+        td = TokenData()
+        self.L.oracle_process_logits(self.m, _fp(row), _ip(t), len(t), int(has_ts), int(seek_delta), C.byref(params),
+                                     float(temperature), _fp(lp), _fp(pr), C.cast(C.byref(td), C.c_void_p))
+        return lp, pr, {f: getattr(td, f) for f, _ in TokenData._fields_}
 
     def full(self, pcm: np.ndarray, params: OracleParams) -> dict:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
