@@ -181,6 +181,25 @@ WHISPER_API void whisper_mi355x_set_gemm_stamps(void * dev);
 WHISPER_API int whisper_mi355x_debug_gemm_small(struct whisper_context * ctx, int epi, const void * A, int M, int K,
                                                 const void * B, int N, const float * bias, void * out,
                                                 const float * ln_w, const float * ln_b, int reps, float * ms);
+/* Test hooks for GGML block-quantized weights (device pointers). A matrix [rows][K] (K % 32 == 0) of ggml type
+ * `type` (2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0) is given as the engine keeps it, the file's blocks regrouped by
+ * field, row-major: qs = the quant bytes [rows][K/2] ([rows][K] for q8_0), qh = the q5 high bits, one u32 per
+ * block [rows][K/32] (NULL for the other types), dm = the f16 scale d per block [rows][K/32], or d then m
+ * [rows][K/32][2] for the *_1 types.
+ * debug_dequant: out[rows][K] (the context's compute type) = the dequantized weights, one launch.
+ * debug_dequant_multi: n <= 6 such matrices by one launch (the per-layer form); all of one type, else nonzero.
+ * debug_gemm_small_q: whisper_mi355x_debug_gemm_small with B given as blocks [N][K], one launch; with epi 0
+ * every output column is multiplied by scale before it is rounded. */
+WHISPER_API int whisper_mi355x_debug_dequant(struct whisper_context * ctx, int type, const void * qs, const void * qh,
+                                             const void * dm, long rows, int K, void * out);
+WHISPER_API int whisper_mi355x_debug_dequant_multi(struct whisper_context * ctx, const int * type, int n,
+                                                   const void * const * qs, const void * const * qh,
+                                                   const void * const * dm, const long * rows, const int * K,
+                                                   void * const * out);
+WHISPER_API int whisper_mi355x_debug_gemm_small_q(struct whisper_context * ctx, int epi, const void * A, int M, int K,
+                                                  int type, const void * qs, const void * qh, const void * dm, int N,
+                                                  const float * bias, float scale, void * out, const float * ln_w,
+                                                  const float * ln_b);
 WHISPER_API void whisper_mi355x_set_dec_splits(int splits); /* 0 = heuristic */
 /* Test hook: the split-K decode GEMM's smallest row tile (32, 64 or 128; 0 = WHISPER_MI355X_DEC_BM or 32).
  * A step takes the smallest tile holding its rows; every value gives the same bits. */

@@ -700,6 +700,66 @@ int whisper_mi355x_debug_gemm_small(struct whisper_context* ctx, int epi, const 
         return 0;
     });
 }
+// GGML block-quantized weights given by field (QMat: qs, qh, dm; qh only for the q5 types)
+static bool debug_qmat(QMat* q, int type, const void* qs, const void* qh, const void* dm) {
+    const bool known = type == 2 || type == 3 || type == 6 || type == 7 || type == 8;
+    if (!known || !qs || !dm || ((type == 6 || type == 7) && !qh)) return false;
+    q->type = type;
+    q->qs = (const uint8_t*)qs;
+    q->qh = (const uint32_t*)qh;
+    q->dm = (const uint16_t*)dm;
+    return true;
+}
+int whisper_mi355x_debug_dequant(struct whisper_context* ctx, int type, const void* qs, const void* qh, const void* dm,
+                                 long rows, int K, void* out) {
+    return guarded(nullptr, [&]() -> int {
+        QMat q;
+        if (!ctx || !out || rows < 1 || K < 1 || !debug_qmat(&q, type, qs, qh, dm)) return -1;
+        hipSetDevice(ctx->c.device);
+        launch_dequant(ctx->c.dt, q, rows, K, out, nullptr);
+        WM_CHECK(hipDeviceSynchronize());
+        return 0;
+    });
+}
+int whisper_mi355x_debug_dequant_multi(struct whisper_context* ctx, const int* type, int n, const void* const* qs,
+                                       const void* const* qh, const void* const* dm, const long* rows, const int* K,
+                                       void* const* out) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !type || !qs || !qh || !dm || !rows || !K || !out || n < 1 || n > 6) return -1;
+        DequantJobs J;
+        J.n = n;
+        for (int j = 0; j < n; j++) {
+            if (!out[j] || rows[j] < 1 || K[j] < 1 || !debug_qmat(&J.q[j], type[j], qs[j], qh[j], dm[j])) return -1;
+            J.rows[j] = rows[j];
+            J.K[j] = K[j];
+            J.out[j] = out[j];
+        }
+        hipSetDevice(ctx->c.device);
+        launch_dequant_multi(ctx->c.dt, J, nullptr);
+        WM_CHECK(hipDeviceSynchronize());
+        return 0;
+    });
+}
+int whisper_mi355x_debug_gemm_small_q(struct whisper_context* ctx, int epi, const void* A, int M, int K, int type,
+                                      const void* qs, const void* qh, const void* dm, int N, const float* bias,
+                                      float scale, void* out, const float* ln_w, const float* ln_b) {
+    return guarded(nullptr, [&]() -> int {
+        QMat q;
+        if (!ctx || !A || !out || N < 1 || !gemm_small_ok(M, K, ln_w != nullptr) || (ln_w && !ln_b) ||
+            !debug_qmat(&q, type, qs, qh, dm))
+            return -1;
+        hipSetDevice(ctx->c.device);
+        GemmArgs g{};
+        g.A = A; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
+        g.B = nullptr; g.q = q; g.bias = bias; g.M = M; g.N = N; g.K = K;
+        g.out = out; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
+        g.sc_div = N; g.sc_mod = 1; g.sc_lim = 1; g.scale = scale;  // every column scaled (EPI_STORE), as the cross-Q call
+        g.a_ln_w = ln_w; g.a_ln_b = ln_b;
+        launch_gemm_small(ctx->c.dt, epi, g, ln_w != nullptr, nullptr);
+        WM_CHECK(hipDeviceSynchronize());
+        return 0;
+    });
+}
 int whisper_mi355x_debug_gemm_fp8(struct whisper_context* ctx, int epi, const void* A8, const float* a_scale, int M,
                                   int K, const void* B8, const float* b_scale, int N, const float* bias, void* out,
                                   int reps, float* ms) {

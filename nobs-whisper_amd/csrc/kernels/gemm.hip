@@ -1417,6 +1417,16 @@ __device__ __forceinline__ u32x4 qraw_load(const QMat& q, long n, int K, int b, 
     r.w = (QT == 3 || QT == 7) ? ((const uint32_t*)q.dm)[bi] : (uint32_t)q.dm[bi];  // d | m << 16, or d
     return r;
 }
+// The f32 value and its conversion to half_t are kept apart by an empty asm (v_mul_f32 / v_fma_f32, then
+// v_cvt_f16_f32). Left together they are selected as one v_fma_mix{lo,hi}_f16, which is not ggml's
+// arithmetic: (half_t)(q * d) becomes fma(q, d, +0), and (-0) + (+0) = +0 loses the sign of a zero product
+// (d = 0 or q = offset); (half_t)(q * d + m) is rounded once from the exact sum, where ggml rounds to f32
+// and then to f16 (a different f16 where the f32 rounding lands on an f16 tie). bf16 has no such instruction.
+template <typename T>
+__device__ __forceinline__ float f32_then_round(float v) {
+    if constexpr (__is_same(T, half_t)) asm("" : "+v"(v));
+    return v;
+}
 template <int QT, typename T>
 __device__ __forceinline__ u32x4 qraw_deq(u32x4 r, int g) {
     const float dd = (float)__builtin_bit_cast(half_t, (uint16_t)(r.w & 0xFFFF));
@@ -1434,7 +1444,7 @@ __device__ __forceinline__ u32x4 qraw_deq(u32x4 r, int g) {
             if constexpr (QT == 3 || QT == 7) v = (float)x * dd + mm;
             else v = (float)(x - (QT == 6 ? 16 : 8)) * dd;
         }
-        o[i] = (T)v;
+        o[i] = (T)f32_then_round<T>(v);
     }
     return *(const u32x4*)o;
 }

@@ -212,6 +212,11 @@ def lib() -> C.CDLL:
         "whisper_mi355x_pdec_give_ups": (C.c_long, [vp]),
         "whisper_mi355x_decoded_tokens_total": (C.c_long, []),
         "whisper_mi355x_debug_ws": (vp, [vp, C.c_int]),
+        "whisper_mi355x_debug_dequant": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_long, C.c_int, vp]),
+        "whisper_mi355x_debug_dequant_multi": (C.c_int, [vp, ip, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                         C.POINTER(C.c_long), ip, C.POINTER(vp)]),
+        "whisper_mi355x_debug_gemm_small_q": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int,
+                                                        vp, C.c_float, vp, vp, vp]),
         "whisper_mi355x_set_pdec_spin": (None, [C.c_long]),
         "whisper_mi355x_set_pdec_stamps": (None, [vp]),
         "whisper_mi355x_set_gemm_stamps": (None, [vp]),
