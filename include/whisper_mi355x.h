@@ -48,11 +48,16 @@ WHISPER_API int whisper_mi355x_broadcast_weights(struct whisper_context * ctx, c
  * 220), else -1. Returns 0 on success.
  * Beam search (params.strategy = WHISPER_SAMPLING_BEAM_SEARCH, here and in whisper_full*): the t = 0 attempt of
  * every window decodes beam_size hypotheses per clip, each beam's candidates being its beam_size most probable
- * tokens after the logits rules (upstream samples them); attempts at t > 0 are single sampled
- * decoders as with the greedy strategy, and patience is ignored. beam_size < 1 counts as 1 (the greedy result,
- * bit for bit), beam_size > 8 returns -4. With beam_size > 1 every live beam of every clip is one row of a
- * cache-form decode step: n_jobs * beam_size <= 32, else -1 (one stderr line). fixed_tokens > 0 with the beam
- * strategy returns -1. */
+ * tokens after the logits rules (upstream samples them); patience is ignored. beam_size < 1 counts
+ * as 1 (the greedy result, bit for bit), beam_size > 8 returns -4. With beam_size > 1 every live beam of every clip
+ * is one row of a cache-form decode step: n_jobs * beam_size <= 32, else -1 (one stderr line). fixed_tokens > 0
+ * with the beam strategy returns -1.
+ * Sampled attempts (t > 0, the temperature fallback) under both strategies decode N = max(1, greedy.best_of)
+ * candidates per clip and keep the best-scoring one, as upstream does. N = 1: one decoder sampled on
+ * the host with std::discrete_distribution. N > 1: the candidates are rows of one cache-form decode step, their
+ * tokens drawn on the device from a counter-based generator (whisper_mi355x_set_sample_seed); this needs
+ * n_jobs * N <= 32, a larger batch samples one host candidate per clip as with N = 1 (one stderr line). N > 8
+ * returns -4. Attempts at t = 0 do not depend on best_of. */
 WHISPER_API int whisper_mi355x_full_batch(struct whisper_context * ctx, struct whisper_state * state,
                                           struct whisper_full_params params, const float * const * pcm,
                                           const int * n_samples, int n_jobs, bool pcm_on_device, int fixed_tokens);
@@ -75,6 +80,16 @@ WHISPER_API int whisper_mi355x_full_batch_forced(struct whisper_context * ctx, s
 #define WHISPER_MI355X_BEAM_WINNER 4
 WHISPER_API int whisper_mi355x_beam_info(struct whisper_state * state, int job, int beam, int * tokens, int cap,
                                          double * sum_logprobs_all, int * flags);
+/* Candidate `cand` of the last sampled attempt with best_of > 1 candidates (device-drawn, see above) of job `job`
+ * of the last full / full_batch call: tokens, sum and flags as whisper_mi355x_beam_info reports a beam. Returns the
+ * token count, or -1 when there is no such candidate (no sampled attempt, best_of <= 1, or the host path). */
+WHISPER_API int whisper_mi355x_cand_info(struct whisper_state * state, int job, int cand, int * tokens, int cap,
+                                         double * sum_logprobs_all, int * flags);
+/* Seed of the device-side draws of this state's sampled candidates (default 0; a recycled state starts at 0 again).
+ * The draw of token i of candidate c in the attempt at temperature index k of the window at `seek` (10 ms frames)
+ * is Philox4x32-10 word 0 of counter (0, seek, 16 k + c, i) under key (seed lo, seed hi): it does not depend on
+ * other clips, attempts or calls. */
+WHISPER_API void whisper_mi355x_set_sample_seed(struct whisper_state * state, uint64_t seed);
 WHISPER_API int whisper_mi355x_batch_n_segments(struct whisper_state * state, int job);
 WHISPER_API const char * whisper_mi355x_batch_segment_text(struct whisper_state * state, int job, int i_segment);
 WHISPER_API int64_t whisper_mi355x_batch_segment_t0(struct whisper_state * state, int job, int i_segment);
@@ -144,7 +159,8 @@ WHISPER_API int whisper_mi355x_get_encoder_out(struct whisper_state * state, flo
  * 2 decoder cross-attention (HBM bytes), 3 decoder self-attention (bytes), 4 decoder GEMM (bytes),
  * 5 logits processing (bytes), 6 mel (bytes), 7 the persistent decode step (bytes), 8 prefill attention
  * (bytes), 9 / 10 / 11 the token-timestamp alignment's score (FLOPs), cost (bytes) and DTW (bytes) kernels,
- * 12 beam search's top-k logits kernel (bytes), 13 its self-cache gather (bytes read + written).
+ * 12 beam search's top-k logits kernel (bytes), 13 its self-cache gather (bytes read + written),
+ * 14 the sampled draw of best_of candidates (bytes: two passes over the rows' probs).
  * class_mask bit k times class k (0 = off); bits 16..23, when > 1, time
  * the decoder's per-layer attention launches (classes 2, 3) of every k-th layer only.
  * Every call resets the counters; stats out = {total ms, launches, total work}. */
@@ -301,6 +317,16 @@ WHISPER_API int whisper_mi355x_debug_logits_topk(struct whisper_context * ctx, c
                                                  struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy);
 WHISPER_API int whisper_mi355x_debug_kv_gather(struct whisper_context * ctx, void * cache, int n_slots, int L, int H,
                                                int n_ctx, const int * copies, int n_copies, int * n_staged);
+
+/* Debug: the sampled draw (kernels/sample.hip) on caller data, one launch. probs = host [n][2][n_vocab] (probs,
+ * logprobs per row, as the logits kernels write them for want_probs rows), rec_in = host [n] records the rows start
+ * from, counters = host [n][3] {seek, 16 * temp_idx + cand, token index}, words = null, or host [n] uniform words
+ * used instead of the Philox word. rec_out (host [n]) receives the rows' records. 1 <= n <= 32, n_vocab <= 65536;
+ * ids >= the context's first timestamp token also set tid and pt. Return 0, -1 on bad arguments, or the runtime
+ * error's negative code. */
+WHISPER_API int whisper_mi355x_debug_sample(struct whisper_context * ctx, const float * probs,
+                                            const struct whisper_mi355x_cand * rec_in, int n, int n_vocab, uint64_t seed,
+                                            const int * counters, const uint32_t * words, struct whisper_mi355x_cand * rec_out);
 
 /* Debug: the greedy logits kernels and the device-side step advance (kernels/logits.hip) on caller data, one
  * launch each through the engine's launcher.

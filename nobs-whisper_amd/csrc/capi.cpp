@@ -485,6 +485,18 @@ int whisper_mi355x_beam_info(struct whisper_state* s, int job, int beam, int* to
     if (flags) *flags = r.flags;
     return (int)r.tokens.size();
 }
+int whisper_mi355x_cand_info(struct whisper_state* s, int job, int cand, int* tokens, int cap, double* sum_logprobs_all,
+                             int* flags) {
+    if (!s || job < 0 || job >= (int)s->cand_info.size() || cand < 0 || cand >= (int)s->cand_info[job].size()) return -1;
+    const whisper_state::BeamRec& r = s->cand_info[job][cand];
+    for (int i = 0; tokens && i < cap && i < (int)r.tokens.size(); i++) tokens[i] = r.tokens[i];
+    if (sum_logprobs_all) *sum_logprobs_all = r.sum_logprobs_all;
+    if (flags) *flags = r.flags;
+    return (int)r.tokens.size();
+}
+void whisper_mi355x_set_sample_seed(struct whisper_state* s, uint64_t seed) {
+    if (s) s->sample_seed = seed;
+}
 int whisper_mi355x_batch_n_segments(struct whisper_state* s, int job) {
     return s && job >= 0 && job < (int)s->results.size() ? (int)s->results[job].size() : 0;
 }
@@ -1008,6 +1020,37 @@ int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* l
             memcpy(&greedy[r], &out[(size_t)n * kTopkMax + r], sizeof(TokOut));
             for (int q = 0; q < k; q++) memcpy(&cand[(size_t)r * k + q], &out[(size_t)r * kTopkMax + q], sizeof(TokOut));
         }
+        return 0;
+    });
+}
+// ---- the sampled draw on caller data (kernels/sample.hip) ---------------------------------------------------------
+int whisper_mi355x_debug_sample(struct whisper_context* ctx, const float* probs, const struct whisper_mi355x_cand* rec_in, int n,
+                                int n_vocab, uint64_t seed, const int* counters, const uint32_t* words,
+                                struct whisper_mi355x_cand* rec_out) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !probs || !rec_in || !counters || !rec_out || n <= 0 || n > kSampleMaxRows || n_vocab < 1 || n_vocab > 65536)
+            return -1;
+        hipSetDevice(ctx->c.device);
+        const size_t pbytes = (size_t)n * 2 * n_vocab * sizeof(float);
+        std::vector<int> ctr((size_t)n * 4);
+        for (int r = 0; r < n; r++) {
+            for (int k = 0; k < 3; k++) ctr[(size_t)r * 4 + k] = counters[(size_t)r * 3 + k];
+            ctr[(size_t)r * 4 + 3] = r;
+        }
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        float* d_probs = (float*)b.get(pbytes);
+        TokOut* d_rec = (TokOut*)b.get(n * sizeof(TokOut));
+        int* d_ctr = (int*)b.get(ctr.size() * sizeof(int));
+        uint32_t* d_words = words ? (uint32_t*)b.get(n * sizeof(uint32_t)) : nullptr;
+        WM_CHECK(hipMemcpyAsync(d_probs, probs, pbytes, hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_rec, rec_in, n * sizeof(TokOut), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_ctr, ctr.data(), ctr.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        if (d_words) WM_CHECK(hipMemcpyAsync(d_words, words, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        launch_sample(d_probs, n_vocab, d_rec, d_rec, d_ctr, d_words, seed, ctx->c.vid.beg, n, st);  // in place, as a step does
+        WM_CHECK(hipMemcpyAsync(rec_out, d_rec, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
         return 0;
     });
 }

@@ -189,6 +189,9 @@ static void reset_for_reuse(whisper_state* s) {
     s->beam_k = 0;
     s->split_slots = false;
     s->beam_info.clear();
+    s->sample_rows = false;
+    s->sample_seed = 0;
+    s->cand_info.clear();
     s->gather_rows = s->gather_rows_full = 0;
     std::fill(s->ws.cross_fresh.begin(), s->ws.cross_fresh.end(), 0);
 }
@@ -289,6 +292,7 @@ void recover_state(whisper_state* s) {
     s->capture_ev = nullptr;
     s->beam_k = 0;  // (an error inside a beam step)
     s->split_slots = false;
+    s->sample_rows = false;
     hipStreamSynchronize(s->stream);
     hipStreamSynchronize(s->stream2);
     (void)hipGetLastError();
@@ -313,8 +317,9 @@ static void free_ws(Workspace& w) {
     dfree(w.lrow); dfree(w.logits); dfree(w.probs); dfree(w.tok); dfree(w.ctl); dfree(w.tout); dfree(w.lrec); dfree(w.win_job);
     dfree(w.pcm); dfree(w.mel); dfree(w.mel_ptrs); dfree(w.splitk); dfree(w.enc); dfree(w.qx); dfree(w.xo);
     dfree(w.xml); dfree(w.kvslot); dfree(w.hs); dfree(w.qtiles); dfree(w.wdq); dfree(w.pd_sync);
-    dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage);
+    dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage); dfree(w.sctr);
     if (w.h_sslot) hipHostFree(w.h_sslot);
+    if (w.h_sctr) hipHostFree(w.h_sctr);
     if (w.h_cand) hipHostFree(w.h_cand);
     if (w.h_kvcp) hipHostFree(w.h_kvcp);
     if (w.h_pd_err) hipHostFree(w.h_pd_err);
@@ -419,9 +424,9 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips
         free_align(w);  // sized by cap_jobs
         for (auto& a : s->align_info) a = {};  // (pointers into al_cost)
         if (w.h_ring) { WM_CHECK(hipHostFree(w.h_ring)); w.h_ring = nullptr; w.ring = nullptr; }
-        dfree(w.sslot); dfree(w.cand); dfree(w.kvcp);
+        dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.sctr);
         for (void** h : {(void**)&w.h_qtiles, (void**)&w.h_ints, (void**)&w.h_tout, (void**)&w.h_ctl, (void**)&w.h_sslot,
-                         (void**)&w.h_cand, (void**)&w.h_kvcp})
+                         (void**)&w.h_cand, (void**)&w.h_kvcp, (void**)&w.h_sctr})
             if (*h) { void* q = *h; *h = nullptr; WM_CHECK(hipHostFree(q)); }
         w.cap_jobs = w.cap_tok = w.cap_cross = w.cap_xq = 0;
         // split-K slabs: decode steps (<= 128 rows per group, two concurrent groups) and the prefill
@@ -470,6 +475,8 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips
         WM_CHECK(hipHostMalloc((void**)&w.h_sslot, (size_t)n_jobs * sizeof(int), 0));
         WM_CHECK(hipHostMalloc((void**)&w.h_cand, (size_t)n_jobs * kTopkMax * sizeof(TokOut), 0));
         WM_CHECK(hipHostMalloc((void**)&w.h_kvcp, (size_t)n_jobs * sizeof(KvCopy), 0));
+        dalloc(w.sctr, (size_t)n_jobs * 4 * sizeof(int));
+        WM_CHECK(hipHostMalloc((void**)&w.h_sctr, (size_t)n_jobs * 4 * sizeof(int), 0));
         w.cap_jobs = n_jobs;
         w.cap_tok = n_tok;
     }
@@ -1442,8 +1449,9 @@ int decode_tokens(Context* c, whisper_state* s, const int* tokens, const int* po
 }
 
 // ---- scheduler ------------------------------------------------------------------------------------
-// (PH_BEAM: the clip's t = 0 attempt decodes as beam_k hypotheses, beam_step)
-enum Phase { PH_ENCODE, PH_LANG, PH_PREFILL, PH_DECODE, PH_BEAM, PH_DONE };
+// (PH_BEAM: the clip's t = 0 attempt decodes as beam_k hypotheses, beam_step; PH_SAMPLE: a t > 0 attempt decodes
+// as best_of candidates drawn on the device, sample_step)
+enum Phase { PH_ENCODE, PH_LANG, PH_PREFILL, PH_DECODE, PH_BEAM, PH_SAMPLE, PH_DONE };
 
 struct Job {
     int slot = 0;
@@ -1510,6 +1518,8 @@ static void swap_dec(Job& j, Beam& b) {
 struct Sched {
     int beam_k = 0;  // > 0: WHISPER_SAMPLING_BEAM_SEARCH with this many beams (t = 0 attempts)
     std::vector<BeamJob> bj;
+    int sample_n = 1;  // > 1: sampled (t > 0) attempts decode this many candidates per clip on the device
+    std::vector<BeamJob> sj;  // their candidates (a candidate is a Beam: decoder state + self slot; `held` is unused)
     Context* c;
     whisper_state* s;
     whisper_full_params p;
@@ -1563,6 +1573,11 @@ static void start_attempt(Sched& S, Job& j) {
     j.prompt.insert(j.prompt.end(), j.prompt_init.begin(), j.prompt_init.end());
 }
 
+// a sampled attempt whose best_of candidates are drawn on the device (else: one host-sampled decoder)
+static bool sample_attempt(const Sched& S, const Job& j) {
+    return S.sample_n > 1 && j.temp_idx > 0 && S.temps[j.temp_idx] >= 1e-6f;
+}
+
 static void fill_ctl(Sched& S, Job& j, SeqCtl& ctl, bool want_nosp) {
     const Vocab& v = S.c->vocab;
     const float t = S.temps[j.temp_idx];
@@ -1579,7 +1594,7 @@ static void fill_ctl(Sched& S, Job& j, SeqCtl& ctl, bool want_nosp) {
         const float precision = float(WHISPER_CHUNK_SIZE) / S.c->hp.n_audio_ctx;
         ctl.tid0_initial = (int)std::round(S.p.max_initial_ts / precision);
     } else ctl.tid0_initial = -1;
-    ctl.want_probs = t >= 1e-6f;
+    ctl.want_probs = t >= 1e-6f ? (sample_attempt(S, j) ? 2 : 1) : 0;
     ctl.want_nosp = want_nosp;
 }
 
@@ -1894,14 +1909,15 @@ static void copy_spot_logits(Sched& S, const std::vector<int>& act) {
 }
 
 // one whisper_full "sample + update" iteration for token index j.step; returns true if decoding continues
-static bool process_step(Sched& S, Job& j, const TokOut& r, const float* probs_row) {
+// (drawn: r is the record of a token drawn on the device, launch_sample, which applied the sampled branch's rules)
+static bool process_step(Sched& S, Job& j, const TokOut& r, const float* probs_row, bool drawn = false) {
     const Vocab& v = S.c->vocab;
     const whisper_full_params& p = S.p;
     const int i = j.step;
     const float t = S.temps[j.temp_idx];
     TokenData td;
     td.tid = r.tid; td.pt = r.pt; td.ptsum = r.ptsum;
-    if (t < 1e-6f) {
+    if (t < 1e-6f || drawn) {
         td.id = r.id; td.p = r.p; td.plog = r.plog;
     } else {
         const int n = v.n_vocab;
@@ -1992,7 +2008,7 @@ static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vect
     if (any_probs) {  // sampling clips (t > 0): probs and logprobs rows for std::discrete_distribution
         const size_t V = c->hp.n_vocab;
         for (int r = 0; r < n; r++)
-            if (w.h_ctl[r].want_probs) {
+            if (w.h_ctl[r].want_probs == 1) {
                 probs_rows[r].resize(2 * V);
                 WM_CHECK(hipMemcpyAsync(probs_rows[r].data(), w.probs + (size_t)r * 2 * V, 2 * V * 4, hipMemcpyDeviceToHost, st));
             }
@@ -2028,7 +2044,7 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     const int n = P.n, pd = P.path == STEP_PDEC;
     P.pipe = par > 0;
     const int sig = dec_path_sig();
-    const int beam = s->beam_k | (s->split_slots ? 1 << 8 : 0);
+    const int beam = s->beam_k | (s->split_slots ? 1 << 8 : 0) | (s->sample_rows ? 1 << 9 : 0);
     // read once: a setter stores its value before it bumps the generation, so a graph captured below under
     // generation `gen` holds that generation's (or a newer) stamps pointer and spin limit, and is retired later
     const int gen = g_pdec_gen.load(std::memory_order_acquire);
@@ -2044,14 +2060,20 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     }
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
-            g.par == par && g.beam == beam)
+            g.par == par && g.beam == beam && (!s->sample_rows || g.seed == s->sample_seed))
             return &g;
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
+    g.seed = s->sample_seed;  // (a kernel argument of the draw below)
     hipGraph_t graph;
     s->capture_ev = &g.ev;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
     decoder_launch(c, s, P);
     logits_launch(c, s, n);
+    if (s->sample_rows) {  // the rows' tokens drawn from their probs, the TokOut records rewritten in place
+        Workspace& w = s->ws;
+        KT kt(s, K_SAMPLE, (double)n * c->hp.n_vocab * 4 * 2);
+        launch_sample(w.probs, c->hp.n_vocab, w.tout, w.tout, w.sctr, nullptr, s->sample_seed, c->vid.beg, n, s->stream);
+    }
     if (par > 0) {
         Workspace& w = s->ws;
         char* slot = w.ring + (par - 1) * ring_slot_bytes(w);
@@ -2549,6 +2571,156 @@ static void beam_step(Sched& S, const std::vector<int>& bjobs) {
     beam_gather(S, copies);
 }
 
+// ---- sampled attempts with best_of candidates ------------------------------------------------------
+// A t > 0 attempt of a clip decodes sample_n candidates: one decoder row per live candidate, the rows of all clips
+// in one cache-form step on the split-K launch chain, as beam steps run. A clip's rows share its cross slot and own
+// their self slots (candidate b of job k: slot b * n_jobs + k; candidate 0 has the clip's own slot, the one the
+// prefill writes). Every row's token is drawn on the device (kernels/sample.hip) from a counter that names the
+// window, the attempt, the candidate and the token index, so only the 32-byte records come back per step, and a
+// candidate's draws do not depend on the step's other rows. Candidates never change parents: the only self-cache
+// copy is the prompt's rows at the start.
+
+// The candidates of the sampled attempts that were just prefilled: `rows` = {job, its row of the prefill's logits
+// launch}. One draw launch takes every candidate's first token from its clip's prefill row (the rows' probs are
+// still in w.probs, their records in w.tout); the prompt's self-cache rows go to the candidates' own slots.
+static void sample_start(Sched& S, const std::vector<std::pair<int, int>>& rows) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const int N = S.sample_n, n_jobs = (int)S.jobs.size(), m = (int)rows.size() * N;
+    if (m > w.cap_jobs || m > kSampleMaxRows) WM_FAIL("best_of: %d candidate rows (at most %d)", m, std::min(w.cap_jobs, kSampleMaxRows));
+    if (s->direct) {  // the steps run in the cache form: the clips' cross K/V from their encoder output
+        std::vector<int> slots;
+        for (auto& jr : rows) slots.push_back(S.jobs[jr.first].slot);
+        ensure_cross(c, s, n_jobs);
+        ensure_cross_cache(c, s, slots);
+    }
+    for (int q = 0; q < (int)rows.size(); q++) {
+        const Job& j = S.jobs[rows[q].first];
+        for (int b = 0; b < N; b++) {
+            int* ctr = w.h_sctr + (size_t)(q * N + b) * 4;
+            ctr[0] = j.seek; ctr[1] = 16 * j.temp_idx + b; ctr[2] = 0; ctr[3] = rows[q].second;
+        }
+    }
+    WM_CHECK(hipMemcpyAsync(w.sctr, w.h_sctr, (size_t)m * 4 * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    {
+        KT kt(s, K_SAMPLE, (double)m * c->hp.n_vocab * 4 * 2);
+        launch_sample(w.probs, c->hp.n_vocab, w.tout, w.cand, w.sctr, nullptr, s->sample_seed, c->vid.beg, m, s->stream);
+    }
+    WM_CHECK(hipMemcpyAsync(w.h_cand, w.cand, (size_t)m * sizeof(TokOut), hipMemcpyDeviceToHost, s->stream));
+    WM_CHECK(hipStreamSynchronize(s->stream));
+    std::vector<KvCopy> copies;
+    for (int q = 0; q < (int)rows.size(); q++) {
+        Job& j = S.jobs[rows[q].first];
+        BeamJob& B = S.sj[rows[q].first];
+        B.beams.assign(N, Beam());
+        for (int b = 0; b < N; b++) {
+            Beam& bm = B.beams[b];
+            bm.sslot = b * n_jobs + j.slot;
+            swap_dec(j, bm);  // (the Job holds a fresh attempt's state: start_attempt)
+            const bool more = process_step(S, j, w.h_cand[q * N + b], nullptr, true);
+            swap_dec(j, bm);
+            bm.ended = !more;
+            if (b > 0 && bm.live()) copies.push_back(KvCopy{bm.sslot, j.slot, 0, (int)j.prompt.size(), 0, 0, 0});
+        }
+        j.phase = PH_SAMPLE;
+    }
+    beam_gather(S, copies);
+}
+
+// One decode step of every live candidate of the `sjobs` clips (all in PH_SAMPLE)
+static void sample_step(Sched& S, const std::vector<int>& sjobs) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    int* hi = w.h_ints;
+    std::vector<std::pair<int, int>> rows;  // {job, candidate}
+    for (int k : sjobs) {
+        Job& j = S.jobs[k];
+        BeamJob& B = S.sj[k];
+        for (int b = 0; b < (int)B.beams.size(); b++) {
+            Beam& bm = B.beams[b];
+            if (!bm.live()) continue;
+            const int r = (int)rows.size();
+            if (r >= w.cap_jobs || r >= kSampleMaxRows) WM_FAIL("best_of: more than %d rows in a step", std::min(w.cap_jobs, kSampleMaxRows));
+            hi[r] = bm.tokens.back().id;
+            hi[w.cap_tok + r] = (int)j.prompt.size() + bm.step;
+            hi[2 * w.cap_tok + r] = j.slot;
+            hi[5 * w.cap_tok + r] = r;
+            w.h_sslot[r] = bm.sslot;
+            int* ctr = w.h_sctr + (size_t)r * 4;
+            ctr[0] = j.seek; ctr[1] = 16 * j.temp_idx + b; ctr[2] = bm.step + 1; ctr[3] = r;
+            swap_dec(j, bm);
+            fill_ctl(S, j, w.h_ctl[r], false);
+            swap_dec(j, bm);
+            rows.push_back({k, b});
+        }
+    }
+    const int n = (int)rows.size();
+    struct Scope {  // the state's switches hold for this step only (also when an error unwinds)
+        whisper_state* s;
+        bool direct;
+        ~Scope() { s->split_slots = false; s->sample_rows = false; s->direct = direct; }
+    } scope{s, s->direct};
+    s->split_slots = true;
+    s->sample_rows = true;
+    s->direct = false;
+    decoder_upload(c, s, n, n, false);
+    WM_CHECK(hipMemcpyAsync(w.sslot, w.h_sslot, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, s->stream));
+    WM_CHECK(hipMemcpyAsync(w.sctr, w.h_sctr, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    whisper_state::DecGraph* G = dec_graph(c, s, dec_path_prepare(c, s, n), 0);
+    if (G->pdec) WM_FAIL("best_of: a sampled step planned the persistent path");
+    WM_CHECK(hipGraphLaunch(G->exec, s->stream));
+    WM_CHECK(hipMemcpyAsync(w.h_tout, w.tout, n * sizeof(TokOut), hipMemcpyDeviceToHost, s->stream));  // the records only
+    WM_CHECK(hipStreamSynchronize(s->stream));
+    kt_flush_graph(s, *G);
+    for (int r = 0; r < n; r++) {
+        Job& j = S.jobs[rows[r].first];
+        Beam& bm = S.sj[rows[r].first].beams[rows[r].second];
+        bm.step++;
+        swap_dec(j, bm);
+        const bool more = process_step(S, j, w.h_tout[r], nullptr, true);
+        swap_dec(j, bm);
+        bm.ended = !more;
+    }
+}
+
+// Score the candidates, pick the winner (beam_winner), hand it to the Job and to attempt_done
+static void sample_finish(Sched& S, int k) {
+    Job& j = S.jobs[k];
+    BeamJob& B = S.sj[k];
+    const int N = (int)B.beams.size();
+    std::vector<double> score(N);
+    std::vector<char> failed(N);
+    std::vector<whisper_state::BeamRec> recs(N);
+    for (int b = 0; b < N; b++) {
+        Beam& bm = B.beams[b];
+        for (const TokenData& t : bm.tokens) recs[b].tokens.push_back(t.id);
+        recs[b].sum_logprobs_all = bm.sum_logprobs_all;
+        if (!bm.failed) {  // as attempt_done scores a single decoder's attempt
+            swap_dec(j, bm);
+            j.tokens.resize(j.result_len);
+            score_seq(S.p, j);
+            if (j.result_len > 32 && j.entropy < S.p.entropy_thold) j.failed = true;
+            swap_dec(j, bm);
+        }
+        score[b] = bm.score;
+        failed[b] = bm.failed;
+        recs[b].flags = (bm.completed ? 1 : 0) | (bm.failed ? 2 : 0);
+    }
+    const int win = beam_winner(score, failed);
+    if (win >= 0) {
+        recs[win].flags |= 4;
+        swap_dec(j, B.beams[win]);
+    } else {
+        j.failed = true;
+    }
+    S.s->cand_info[k] = std::move(recs);
+    B.beams.clear();
+    attempt_done(S, j);
+}
+
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                           int n_jobs, bool on_device, const FullOpts& o, bool single_api);
 
@@ -2610,6 +2782,7 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
         s->decisions.push_back(std::move(t->decisions[j]));
         s->align_info.push_back(t->align_info[j]);  // (its cost matrix stays in the twin's workspace)
         s->beam_info.push_back(std::move(t->beam_info[j]));
+        s->cand_info.push_back(std::move(t->cand_info[j]));
     }
     s->align_ms = std::max(s->align_ms, t->align_ms);
     s->decoded_tokens += t->decoded_tokens;
@@ -2652,21 +2825,35 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
         fprintf(stderr, "whisper_mi355x: unknown sampling strategy %d\n", (int)p.strategy);
         return -100;
     }
-    if (p.strategy == WHISPER_SAMPLING_GREEDY && p.greedy.best_of > 1) {
-        // whisper.cpp uses best_of only for sampled (t > 0) fallback attempts: t = 0 is unaffected.
-        // Sampled attempts here run one candidate per clip (the reference's Greedy{best_of: 1}).
+    // whisper.cpp uses best_of for sampled (t > 0) fallback attempts only, under both strategies: t = 0 is unaffected.
+    // (the fixed-work mode has no fallback)
+    int sample_n = o.fixed_tokens > 0 ? 1 : std::max(1, p.greedy.best_of);
+    if (sample_n > kBeamMax) {
+        fprintf(stderr, "whisper_mi355x: best_of %d > %d\n", sample_n, kBeamMax);
+        return -4;
+    }
+    if (sample_n > 1 && (long)n_jobs * sample_n > kBeamMaxRows) {
+        // every candidate is a decoder row with its own self slot; above the row limit sampled attempts run one
+        // host-sampled candidate per clip (the reference's Greedy{best_of: 1})
         static bool warned = false;
-        if (!warned) fprintf(stderr, "whisper_mi355x: greedy best_of=%d: fallback attempts sample 1 candidate\n", p.greedy.best_of);
+        if (!warned)
+            fprintf(stderr, "whisper_mi355x: best_of=%d x %d clips exceeds %d decoder rows per step: fallback attempts sample 1 candidate\n",
+                    sample_n, n_jobs, kBeamMaxRows);
         warned = true;
+        sample_n = 1;
     }
     ensure_expanded(c, s->stream);  // quantized files: before anything is captured
     Sched S;
     S.c = c; S.s = s; S.p = p; S.o = o; S.single_api = single_api;
     S.beam_k = beam_k;
     S.bj.resize(beam_k > 0 ? n_jobs : 0);
+    S.sample_n = sample_n;
+    S.sj.resize(sample_n > 1 ? n_jobs : 0);
     s->beam_info.assign(n_jobs, {});
+    s->cand_info.assign(n_jobs, {});
     s->beam_k = 0;
     s->split_slots = false;
+    s->sample_rows = false;
     const Vocab& v = c->vocab;
     const Hparams& hp = c->hp;
     s->results.assign(n_jobs, {});
@@ -2678,7 +2865,9 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     double t0 = now_ms();
     // beams of one clip share its cross K/V cache slot: beam_k > 1 runs in the cache form, with a self slot per beam
     s->direct = beam_k > 1 ? false : pick_direct(c, n_jobs);
-    ensure_ws(c, s, beam_k > 1 ? n_jobs * beam_k : n_jobs, n_jobs);
+    // (best_of candidates take self slots like beams, but the call keeps its own cross form: the t = 0 attempt's plan
+    // is the one it takes with best_of = 1)
+    ensure_ws(c, s, n_jobs * std::max(1, std::max(beam_k, sample_n)), n_jobs);
     compute_mel(c, s, pcm, n, n_jobs, on_device);
     S.t_mel = now_ms() - t0;
 
@@ -2847,9 +3036,14 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 S.t_prefill += now_ms() - tp;
                 copy_spot_logits(S, act);
                 std::vector<KvCopy> copies;
+                std::vector<std::pair<int, int>> srows;  // sampled attempts with best_of candidates: {job, row}
                 for (int r = 0; r < (int)act.size(); r++) {
                     Job& j = S.jobs[act[r]];
                     j.no_speech_prob = w.h_tout[r].nosp_prob;
+                    if (sample_attempt(S, j)) {
+                        srows.push_back({act[r], r});
+                        continue;
+                    }
                     if (beam_attempt(S, j)) {
                         beam_start(S, act[r], w.h_cand + (size_t)r * kTopkMax, copies);
                         j.phase = PH_BEAM;
@@ -2861,6 +3055,11 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 if (!copies.empty()) {  // the prompt's rows from every clip's own slot to its other beams' slots
                     const double tg = now_ms();
                     beam_gather(S, copies);
+                    S.t_decode += now_ms() - tg;
+                }
+                if (!srows.empty()) {
+                    const double tg = now_ms();
+                    sample_start(S, srows);
                     S.t_decode += now_ms() - tg;
                 }
             }
@@ -2905,6 +3104,24 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
                 const double td = now_ms();
                 beam_step(S, bjobs);
+                S.t_decode += now_ms() - td;
+            }
+        }
+        // ---- sampled attempts with best_of candidates: one step for the live candidates of every such clip; a clip
+        // without live candidates ends its attempt (also right after the prefill)
+        {
+            std::vector<int> sjobs;
+            for (int k = 0; k < n_jobs; k++) {
+                if (S.jobs[k].phase != PH_SAMPLE) continue;
+                bool live = false;
+                for (const Beam& b : S.sj[k].beams) live |= b.live();
+                if (live) sjobs.push_back(k);
+                else sample_finish(S, k);
+            }
+            if (!sjobs.empty()) {
+                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
+                const double td = now_ms();
+                sample_step(S, sjobs);
                 S.t_decode += now_ms() - td;
             }
         }

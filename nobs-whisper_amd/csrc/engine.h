@@ -191,6 +191,7 @@ struct Workspace {
     // slot in `slot`), the top-k candidates [cap_jobs][kTopkMax] of the logits rows, the self-cache copies of a
     // re-parenting and the gather's staging buffer (grown on demand, 16-byte units)
     int *sslot = nullptr, *h_sslot = nullptr;
+    int *sctr = nullptr, *h_sctr = nullptr;  // sampled draws: [cap_jobs][4] {seek, 16 * temp_idx + cand, token index, source row}
     TokOut *cand = nullptr, *h_cand = nullptr;
     KvCopy *kvcp = nullptr, *h_kvcp = nullptr;
     void* kvstage = nullptr;
@@ -225,7 +226,7 @@ struct Job;
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
-              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_NCLASS };
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 }  // namespace wm
@@ -276,8 +277,9 @@ struct whisper_state {
     // (par: 0 for the per-step path; the pipelined path alternates two instances, 0 and 1, so that one step's
     // graph events are read while the other instance runs)
     // (beam: 0 for greedy steps; a beam-search step's graph ends with the top-k kernel for beam_k candidates and,
-    // with split_slots, reads the rows' self slots from ws.sslot: beam_k | split_slots << 8)
-    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; };
+    // with split_slots, reads the rows' self slots from ws.sslot: beam_k | split_slots << 8; a sampled step of best_of
+    // candidates ends with the draw kernel over the rows' probs: | 1 << 9, and `seed` = the draw's key)
+    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
     double cur_self_work = 0;                     // self-attention bytes of the current step
@@ -297,6 +299,12 @@ struct whisper_state {
     bool split_slots = false;
     struct BeamRec { std::vector<int> tokens; double sum_logprobs_all = 0; int flags = 0; };
     std::vector<std::vector<BeamRec>> beam_info;
+    // sampled attempts with best_of > 1 candidates. sample_rows: true while such a step runs (its
+    // graph ends with launch_sample over ws.sctr); sample_seed: the draws' Philox key; cand_info[job] = the
+    // candidates of the job's last such attempt (whisper_mi355x_cand_info).
+    bool sample_rows = false;
+    uint64_t sample_seed = 0;
+    std::vector<std::vector<BeamRec>> cand_info;
     // cache rows the gather moved since the state was created, and what whole-sequence copies would have moved
     double gather_rows = 0, gather_rows_full = 0;
 };

@@ -300,7 +300,7 @@ struct SeqCtl {             // per-sequence inputs of whisper_process_logits
     int is_initial, last_ts, penult_ts, has_ts, seek_delta;
     float temperature;
     int suppress_blank, no_timestamps, suppress_eot, tid0_initial;  // tid0_initial < 0: no max_initial_ts rule
-    int want_probs, want_nosp;
+    int want_probs, want_nosp;  // want_probs: 1 = the probs row goes to the host's sampler, 2 = it stays on the device (launch_sample)
 };
 struct TokOut { int id, tid; float p, plog, pt, ptsum, nosp_prob, pad; };
 // rec: scratch of logits_rec_bytes(n_seq) bytes for the split form (rows spread over several workgroups
@@ -315,6 +315,17 @@ size_t logits_rec_bytes(int n_seq);
 constexpr int kTopkMax = 8;
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
                         void* rec, hipStream_t st);
+// ---- sampled draw (kernels/sample.hip; best_of candidates of a t > 0 attempt) -------
+// Row r < n (<= kSampleMaxRows, one workgroup each) draws a token from probs row src = ctr[r][3] of the
+// [.][2][n_vocab] buffer launch_logits fills for want_probs rows: uniform word x0 = words[r] if words, else
+// Philox4x32-10 word 0 of counter (0, ctr[r][0], ctr[r][1], ctr[r][2]) = (0, seek, 16 * temp_idx + cand, token
+// index) under key `seed`; id = the first id whose inclusive prefix sum (double, ascending id) exceeds
+// (x0 + 0.5) * 2^-32 * total. out[r] = in[src] with id, p, plog of the drawn token (and tid = id, pt = p when
+// id >= token_beg); a row whose probs sum to 0 keeps in[src]. in == out is allowed when src == r for every row.
+// ctr: device [n][4] ints.
+constexpr int kSampleMaxRows = 32;
+void launch_sample(const float* probs, int n_vocab, const TokOut* in, TokOut* out, const int* ctr, const uint32_t* words,
+                   uint64_t seed, int token_beg, int n, hipStream_t st);
 // ---- self-cache gather (kernels/beam.hip; beam search re-parenting) --------------------------------
 // Every copy of the list (beam.h KvCopy, scheduled by beam_schedule) moves rows [row0, row1) of K and V of every
 // layer and head of the cache [n_slots][L][2][H][n_ctx][64] (2-byte type) from src_slot to dst_slot, as a

@@ -174,6 +174,10 @@ def lib() -> C.CDLL:
         "whisper_mi355x_full_batch_forced": (C.c_int, [vp, vp, FullParams, C.POINTER(vp), ip, C.c_int, C.c_bool, C.c_int,
                                                        ip, ip, C.c_int, C.POINTER(C.c_float)]),
         "whisper_mi355x_beam_info": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(C.c_double), ip]),
+        "whisper_mi355x_cand_info": (C.c_int, [vp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(C.c_double), ip]),
+        "whisper_mi355x_set_sample_seed": (None, [vp, C.c_uint64]),
+        "whisper_mi355x_debug_sample": (C.c_int, [vp, fp, C.POINTER(Cand), C.c_int, C.c_int, C.c_uint64, ip,
+                                                  C.POINTER(C.c_uint32), C.POINTER(Cand)]),
         "whisper_mi355x_debug_logits_topk": (C.c_int, [vp, vp, C.c_int, ip, fp, C.c_int, C.c_int, C.POINTER(Cand),
                                                        C.POINTER(Cand)]),
         "whisper_mi355x_debug_kv_gather": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip]),
@@ -446,6 +450,26 @@ class WhisperState:
                 return out
             out.append(dict(tokens=list(toks[:n]), sum_logprobs_all=sm.value, completed=bool(fl.value & BEAM_COMPLETED),
                             failed=bool(fl.value & BEAM_FAILED), winner=bool(fl.value & BEAM_WINNER)))
+
+    def cand_info(self, job: int = 0) -> list:
+        """whisper_mi355x_cand_info: the candidates of the job's last sampled attempt with best_of > 1 (drawn on the
+        device), as beam_info's dicts; [] when there is none."""
+        out = []
+        ip_ = C.POINTER(C.c_int)
+        while True:
+            cap = 512
+            toks = (C.c_int * cap)()
+            sm = C.c_double(0)
+            fl = C.c_int(0)
+            n = self.L.whisper_mi355x_cand_info(self.ptr, job, len(out), C.cast(toks, ip_), cap, C.byref(sm), C.byref(fl))
+            if n < 0:
+                return out
+            out.append(dict(tokens=list(toks[:n]), sum_logprobs_all=sm.value, completed=bool(fl.value & BEAM_COMPLETED),
+                            failed=bool(fl.value & BEAM_FAILED), winner=bool(fl.value & BEAM_WINNER)))
+
+    def set_sample_seed(self, seed: int) -> None:
+        """whisper_mi355x_set_sample_seed: the key of the device-side draws of sampled candidates (default 0)."""
+        self.L.whisper_mi355x_set_sample_seed(self.ptr, seed & 0xFFFFFFFFFFFFFFFF)
 
     def decisions(self, job: int = 0) -> list:
         """Per-window temperature-fallback decisions of the last full (job 0) / full_batch call."""
