@@ -31,6 +31,10 @@
  * keeps beam_size <= 8 hypotheses per window at t = 0 and extends each by its beam_size most probable tokens after
  * the logits rules, where upstream draws them from the softmax; patience is accepted and ignored; attempts at t > 0
  * are single sampled decoders, as with the greedy strategy (whisper_mi355x.h).
+ *
+ * whisper_full_params.token_timestamps, thold_pt, thold_ptsum, max_len and split_on_word are implemented (DESIGN.md §13,
+ * whisper_mi355x.h). Still accepted and ignored: audio_ctx, suppress_nst, suppress_regex, the grammar fields,
+ * tdrz_enable and vad (with vad_model_path and vad_params).
  */
 #ifndef WHISPER_H
 #define WHISPER_H

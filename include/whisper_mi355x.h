@@ -148,6 +148,37 @@ WHISPER_API double whisper_mi355x_align_ms(struct whisper_state * state);
 WHISPER_API int whisper_mi355x_align_cost(struct whisper_state * state, int job, float * out, long cap_floats,
                                           int * rows, int * frames);
 
+/* Per-token t0 / t1 / vlen and line-length-limited segments (whisper_full_params.token_timestamps, thold_pt,
+ * thold_ptsum, max_len, split_on_word; whisper-rs set_token_timestamps, set_max_len, set_split_on_word).
+ * With token_timestamps set, every token of whisper_full_get_token_data* and whisper_mi355x_batch_token_data carries
+ * t0, t1 (10 ms units, absolute within the clip) and vlen: placed from the timestamp tokens, the intervals between them
+ * spread by voice length, then adjusted on the clip's smoothed energy signal (a 65-tap mean of |pcm|, computed on the
+ * device once per call); with max_len > 0 as well, every segment is cut into pieces of at most max_len bytes of text
+ * (split_on_word: only before a token that starts with a space), and the segment getters, whisper_full_n_segments and
+ * the new-segment callback's n_new see the pieces. Without token_timestamps the five fields change nothing: t0 = t1 =
+ * -1, vlen = 0, no segment is cut.
+ * whisper_mi355x_token_times_ms: wall time of these passes in the last full / full_batch call (0 when off; not part
+ * of whisper_mi355x_phase_ms' five slots). */
+WHISPER_API double whisper_mi355x_token_times_ms(struct whisper_state * state);
+/* Debug: the two token-time kernels (kernels/tokts.hip) on caller data, host pointers, one launch each.
+ * Clips are concatenated: clip c of n_samples[c] >= 1 samples starts at the running offset rounded up to 64 floats,
+ * in pcm, energy and energy_out alike (so each holds sum of n_samples[c] rounded up to 64 floats).
+ * signal_energy: energy_out[i] = (sum_{j=-32..32, inside the clip} |pcm[i + j]|) / 65.0f per clip, the f32 sum taken
+ * from 0.0f in ascending j (the padding between clips comes back as 0).
+ * token_vad: segment q of seg_n_tokens[q] >= 2 tokens belongs to clip seg_clip[q]; spans holds the segments' tokens
+ * back to back, in / out: t0, t1 in 10 ms units, is_text = 0 for a token the pass leaves as it is (ids >= eot).
+ * Both return 0, or -1 on bad arguments (a clip index out of range, n_samples < 1, a segment of fewer than 2 tokens),
+ * and then launch nothing. */
+struct whisper_mi355x_token_span {
+    int64_t t0, t1;
+    int32_t is_text, pad;
+};
+WHISPER_API int whisper_mi355x_debug_signal_energy(struct whisper_context * ctx, const float * pcm, const int * n_samples,
+                                                   int n_clips, float * energy_out);
+WHISPER_API int whisper_mi355x_debug_token_vad(struct whisper_context * ctx, const float * energy, const int * n_samples,
+                                               int n_clips, const int * seg_clip, const int * seg_n_tokens, int n_segs,
+                                               struct whisper_mi355x_token_span * spans);
+
 /* Normalised log-mel of the last whisper_pcm_to_mel_with_state / whisper_full_with_state call,
  * copied to host: [n_mel][n_len] f32. Returns n_len. */
 WHISPER_API int whisper_mi355x_get_mel(struct whisper_state * state, float * out, int cap_floats);
@@ -160,7 +191,8 @@ WHISPER_API int whisper_mi355x_get_encoder_out(struct whisper_state * state, flo
  * 5 logits processing (bytes), 6 mel (bytes), 7 the persistent decode step (bytes), 8 prefill attention
  * (bytes), 9 / 10 / 11 the token-timestamp alignment's score (FLOPs), cost (bytes) and DTW (bytes) kernels,
  * 12 beam search's top-k logits kernel (bytes), 13 its self-cache gather (bytes read + written),
- * 14 the sampled draw of best_of candidates (bytes: two passes over the rows' probs).
+ * 14 the sampled draw of best_of candidates (bytes: two passes over the rows' probs),
+ * 15 the token-time kernels (signal energy and the voice-activity adjust; bytes).
  * class_mask bit k times class k (0 = off); bits 16..23, when > 1, time
  * the decoder's per-layer attention launches (classes 2, 3) of every k-th layer only.
  * Every call resets the counters; stats out = {total ms, launches, total work}. */

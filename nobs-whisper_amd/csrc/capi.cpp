@@ -395,7 +395,7 @@ static whisper_token_data tdata(const Segment* g, int t) {
     if (!g || t < 0 || t >= (int)g->tokens.size()) { r.id = -1; return r; }
     const TokenData& x = g->tokens[t];
     r.id = x.id; r.tid = x.tid; r.p = x.p; r.plog = x.plog; r.pt = x.pt; r.ptsum = x.ptsum;
-    r.t0 = -1; r.t1 = -1; r.t_dtw = x.t_dtw; r.vlen = 0.0f;
+    r.t0 = x.t0; r.t1 = x.t1; r.t_dtw = x.t_dtw; r.vlen = x.vlen;  // (-1, -1, 0 without token_timestamps)
     return r;
 }
 whisper_token_data whisper_full_get_token_data_from_state(struct whisper_state* s, int i, int t) { return tdata(seg(s, 0, i), t); }
@@ -1050,6 +1050,81 @@ int whisper_mi355x_debug_sample(struct whisper_context* ctx, const float* probs,
         if (d_words) WM_CHECK(hipMemcpyAsync(d_words, words, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         launch_sample(d_probs, n_vocab, d_rec, d_rec, d_ctr, d_words, seed, ctx->c.vid.beg, n, st);  // in place, as a step does
         WM_CHECK(hipMemcpyAsync(rec_out, d_rec, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+// ---- the token-time kernels on caller data (kernels/tokts.hip) -----------------------------------------------------
+double whisper_mi355x_token_times_ms(struct whisper_state* s) { return s ? s->tokts_ms : 0.0; }
+// clip c starts at the running offset rounded up to 64 floats; false when a clip has fewer than 1 sample
+static bool tt_hook_clips(const int* n_samples, int n_clips, std::vector<TtClip>& cl, size_t& total, int& max_n) {
+    cl.resize(n_clips);
+    total = 0;
+    max_n = 0;
+    for (int c = 0; c < n_clips; c++) {
+        if (n_samples[c] < 1) return false;
+        cl[c] = TtClip{nullptr, (long long)total, n_samples[c], 0};
+        total += ((size_t)n_samples[c] + 63) & ~(size_t)63;
+        max_n = std::max(max_n, n_samples[c]);
+    }
+    return true;
+}
+int whisper_mi355x_debug_signal_energy(struct whisper_context* ctx, const float* pcm, const int* n_samples, int n_clips,
+                                       float* energy_out) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !pcm || !n_samples || !energy_out || n_clips < 1 || n_clips > 65535) return -1;
+        std::vector<TtClip> cl;
+        size_t total;
+        int max_n;
+        if (!tt_hook_clips(n_samples, n_clips, cl, total, max_n)) return -1;
+        hipSetDevice(ctx->c.device);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        float* d_pcm = (float*)b.get(total * sizeof(float));
+        float* d_e = (float*)b.get(total * sizeof(float));
+        TtClip* d_cl = (TtClip*)b.get(cl.size() * sizeof(TtClip));
+        for (TtClip& c : cl) c.pcm = d_pcm + c.e_off;
+        WM_CHECK(hipMemcpyAsync(d_pcm, pcm, total * sizeof(float), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemsetAsync(d_e, 0, total * sizeof(float), st));  // (the padding between clips)
+        WM_CHECK(hipMemcpyAsync(d_cl, cl.data(), cl.size() * sizeof(TtClip), hipMemcpyHostToDevice, st));
+        launch_signal_energy(d_cl, n_clips, max_n, d_e, st);
+        WM_CHECK(hipMemcpyAsync(energy_out, d_e, total * sizeof(float), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+static_assert(sizeof(whisper_mi355x_token_span) == sizeof(TtSpan), "whisper_mi355x_token_span mirrors TtSpan");
+int whisper_mi355x_debug_token_vad(struct whisper_context* ctx, const float* energy, const int* n_samples, int n_clips,
+                                   const int* seg_clip, const int* seg_n_tokens, int n_segs,
+                                   struct whisper_mi355x_token_span* spans) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !energy || !n_samples || !seg_clip || !seg_n_tokens || !spans || n_clips < 1 || n_segs < 1) return -1;
+        std::vector<TtClip> cl;
+        size_t total;
+        int max_n;
+        if (!tt_hook_clips(n_samples, n_clips, cl, total, max_n)) return -1;
+        std::vector<TtSeg> sg(n_segs);
+        long n_tok = 0;
+        for (int q = 0; q < n_segs; q++) {
+            if (seg_clip[q] < 0 || seg_clip[q] >= n_clips || seg_n_tokens[q] < 2 || n_tok + seg_n_tokens[q] > INT32_MAX) return -1;
+            sg[q] = TtSeg{seg_clip[q], (int)n_tok, seg_n_tokens[q], 0};
+            n_tok += seg_n_tokens[q];
+        }
+        hipSetDevice(ctx->c.device);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        float* d_e = (float*)b.get(total * sizeof(float));
+        TtClip* d_cl = (TtClip*)b.get(cl.size() * sizeof(TtClip));
+        TtSeg* d_sg = (TtSeg*)b.get(sg.size() * sizeof(TtSeg));
+        TtSpan* d_sp = (TtSpan*)b.get((size_t)n_tok * sizeof(TtSpan));
+        WM_CHECK(hipMemcpyAsync(d_e, energy, total * sizeof(float), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_cl, cl.data(), cl.size() * sizeof(TtClip), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_sg, sg.data(), sg.size() * sizeof(TtSeg), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(d_sp, spans, (size_t)n_tok * sizeof(TtSpan), hipMemcpyHostToDevice, st));
+        launch_token_vad(d_e, d_cl, d_sg, n_segs, d_sp, st);
+        WM_CHECK(hipMemcpyAsync(spans, d_sp, (size_t)n_tok * sizeof(TtSpan), hipMemcpyDeviceToHost, st));
         WM_CHECK(hipStreamSynchronize(st));
         return 0;
     });

@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "engine.h"
+#include "token_times.h"
 
 namespace wm {
 
@@ -175,6 +176,7 @@ static void reset_for_reuse(whisper_state* s) {
     s->logits_host.clear();
     for (double& t : s->phase_ms) t = 0;
     s->align_ms = 0;
+    s->tokts_ms = 0;
     s->align_info.clear();
     s->decoded_tokens = 0;
     s->last_enc_windows = 0;
@@ -318,6 +320,7 @@ static void free_ws(Workspace& w) {
     dfree(w.pcm); dfree(w.mel); dfree(w.mel_ptrs); dfree(w.splitk); dfree(w.enc); dfree(w.qx); dfree(w.xo);
     dfree(w.xml); dfree(w.kvslot); dfree(w.hs); dfree(w.qtiles); dfree(w.wdq); dfree(w.pd_sync);
     dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage); dfree(w.sctr);
+    dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans);
     if (w.h_sslot) hipHostFree(w.h_sslot);
     if (w.h_sctr) hipHostFree(w.h_sctr);
     if (w.h_cand) hipHostFree(w.h_cand);
@@ -574,6 +577,45 @@ int compute_mel(Context* c, whisper_state* s, const float* const* pcm, const int
     s->n_len_org = mel_n_len_org(n[0]);
     s->mel_ready = true;
     return 0;
+}
+
+// ---- token times: the clips' energy signals (whisper_full_params.token_timestamps) -------------
+template <typename T> static void tt_grow(T*& p, int& cap, size_t need) {
+    if ((size_t)cap >= need) return;
+    dfree(p);
+    cap = 0;
+    const size_t n = std::max(need, (size_t)64);
+    dalloc(p, n * sizeof(T));
+    cap = (int)n;
+}
+
+// After compute_mel of the same call, from the same device PCM: the caller's buffers (on_device), else w.pcm,
+// where compute_mel put every clip on a 64-float boundary. The energy buffer has that layout.
+static void compute_energy(whisper_state* s, const float* const* pcm, const int* n, int n_jobs, bool on_device) {
+    Workspace& w = s->ws;
+    std::vector<TtClip> cl(n_jobs);
+    size_t off = 0;
+    int max_n = 0;
+    double bytes = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        cl[j] = TtClip{on_device ? pcm[j] : w.pcm + off, (long long)off, n[j], 0};
+        off += ((size_t)n[j] + 63) & ~(size_t)63;
+        max_n = std::max(max_n, n[j]);
+        bytes += 8.0 * n[j];
+    }
+    if (off > w.cap_energy) {
+        dfree(w.energy);
+        w.cap_energy = 0;
+        dalloc(w.energy, off * 4);
+        w.cap_energy = off;
+    }
+    tt_grow(w.tt_clips, w.tt_cap_clips, (size_t)n_jobs);
+    WM_CHECK(hipMemcpyAsync(w.tt_clips, cl.data(), cl.size() * sizeof(TtClip), hipMemcpyHostToDevice, s->stream));
+    {
+        KT kt(s, K_TOKTS, bytes);
+        launch_signal_energy(w.tt_clips, n_jobs, max_n, w.energy, s->stream);
+    }
+    WM_CHECK(hipStreamSynchronize(s->stream));  // cl (pageable) must outlive the copy
 }
 
 // ---- encoder + cross KV ---------------------------------------------------------------------------
@@ -1480,6 +1522,11 @@ struct Job {
     bool al_pending = false;
     int al_seek = 0, al_frames = 0;
     size_t al_seg0 = 0;
+    // token times of the window that just finished (finish_window -> token_time_windows): its first new segment, and
+    // the clip's state, which lives for this call
+    bool tt_pending = false;
+    size_t tt_seg0 = 0;
+    TtState tt;
 };
 
 // Beam search: a beam is the decoder part of a Job plus its self-cache slot. The per-token code
@@ -1529,7 +1576,7 @@ struct Sched {
     bool single_api;
     int n_max_steps;
     long decoded = 0;
-    double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0;
+    double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0, t_tokts = 0;
 };
 
 static double now_ms() {
@@ -1642,6 +1689,10 @@ static void finish_window(Sched& S, Job& j) {
         j.al_seek = j.seek;
         j.al_frames = std::min(std::min(3000, seek_delta), j.seek_end - j.seek);
         j.al_seg0 = n_before;
+    }
+    if (p.token_timestamps && j.n_new_segments > 0) {  // placed by token_time_windows, after align_windows
+        j.tt_pending = true;
+        j.tt_seg0 = n_before;
     }
     j.dec.seek = j.seek;
     j.dec.temp_idx = j.temp_idx;
@@ -1889,6 +1940,92 @@ static void align_windows(Sched& S) {
         i0 = i1;
     }
     S.t_align += now_ms() - t0;
+}
+
+// Token times of every window that just finished with new segments (Job::tt_pending), whatever attempt decided it
+// (greedy, beam, sampled: the segments hold the kept sequence's tokens). Per new segment, in order: phase 1 on the
+// host (token_times.cpp) with the clip's state; then the voice-activity adjust of every segment of two tokens or more,
+// all clips in one launch, only the {t0, t1, is_text} records crossing the bus; then, with max_len > 0, the wrap.
+// Runs after align_windows, which holds pointers into the token vectors the wrap rebuilds (and so the pieces carry
+// their t_dtw), and before the new-segment callback.
+static void token_time_windows(Sched& S) {
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const Vocab& v = S.c->vocab;
+    const whisper_full_params& p = S.p;
+    std::vector<int> pend;
+    for (int k = 0; k < (int)S.jobs.size(); k++)
+        if (S.jobs[k].tt_pending) pend.push_back(k);
+    if (pend.empty()) return;
+    const double t_start = now_ms();
+    std::vector<TtSeg> segs;
+    std::vector<TtSpan> spans;
+    struct Ref { int job; size_t seg; };
+    std::vector<Ref> refs;
+    std::vector<TtTok> tok;
+    double bytes = 0;
+    for (int k : pend) {
+        Job& j = S.jobs[k];
+        if (j.n_samples < 1) continue;  // no energy: the tokens keep t0 = t1 = -1
+        for (size_t g = j.tt_seg0; g < j.result.size(); g++) {
+            Segment& sg = j.result[g];
+            tok.assign(sg.tokens.size(), TtTok());
+            for (size_t i = 0; i < tok.size(); i++) {
+                const TokenData& td = sg.tokens[i];
+                tok[i].id = td.id; tok[i].tid = td.tid; tok[i].pt = td.pt; tok[i].ptsum = td.ptsum;
+            }
+            tt_phase1(tok, sg.t0, sg.t1, j.tt, v.token_beg, p.thold_pt, p.thold_ptsum, v.id_to_token);
+            for (size_t i = 0; i < tok.size(); i++) {
+                TokenData& td = sg.tokens[i];
+                td.t0 = tok[i].t0; td.t1 = tok[i].t1; td.vlen = tok[i].vlen;
+            }
+            if (tok.size() < 2) continue;
+            segs.push_back(TtSeg{k, (int)spans.size(), (int)tok.size(), 0});
+            refs.push_back({k, g});
+            for (const TtTok& t : tok) {
+                const bool text = t.id < v.token_eot;
+                spans.push_back(TtSpan{t.t0, t.t1, text ? 1 : 0, 0});
+                if (text) bytes += 4.0 * std::min<double>(j.n_samples, 160.0 * (double)std::max<int64_t>(0, t.t1 - t.t0) + 4000.0);
+            }
+        }
+    }
+    if (!segs.empty()) {
+        hipStream_t st = s->stream;
+        tt_grow(w.tt_segs, w.tt_cap_segs, segs.size());
+        tt_grow(w.tt_spans, w.tt_cap_spans, spans.size());
+        WM_CHECK(hipMemcpyAsync(w.tt_segs, segs.data(), segs.size() * sizeof(TtSeg), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemcpyAsync(w.tt_spans, spans.data(), spans.size() * sizeof(TtSpan), hipMemcpyHostToDevice, st));
+        {
+            KT kt(s, K_TOKTS, bytes + 2.0 * spans.size() * sizeof(TtSpan));
+            launch_token_vad(w.energy, w.tt_clips, w.tt_segs, (int)segs.size(), w.tt_spans, st);
+        }
+        WM_CHECK(hipMemcpyAsync(spans.data(), w.tt_spans, spans.size() * sizeof(TtSpan), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        for (size_t q = 0; q < segs.size(); q++) {
+            Segment& sg = S.jobs[refs[q].job].result[refs[q].seg];
+            for (int i = 0; i < segs[q].n_tok; i++) {
+                sg.tokens[i].t0 = spans[segs[q].tok0 + i].t0;
+                sg.tokens[i].t1 = spans[segs[q].tok0 + i].t1;
+            }
+        }
+    }
+    for (int k : pend) {
+        Job& j = S.jobs[k];
+        j.tt_pending = false;
+        if (p.max_len <= 0) continue;
+        std::vector<Segment> out(std::make_move_iterator(j.result.begin() + j.tt_seg0), std::make_move_iterator(j.result.end()));
+        j.result.resize(j.tt_seg0);
+        for (Segment& sg : out) {
+            tok.assign(sg.tokens.size(), TtTok());
+            for (size_t i = 0; i < tok.size(); i++) { tok[i].id = sg.tokens[i].id; tok[i].t0 = sg.tokens[i].t0; }
+            for (TtPiece& pc : tt_wrap(tok, sg.t0, sg.t1, p.max_len, p.split_on_word, v.token_eot, v.id_to_token)) {
+                j.result.push_back({pc.t0, pc.t1, std::move(pc.text), sg.no_speech_prob, {}});
+                j.result.back().tokens.assign(sg.tokens.begin() + pc.i0, sg.tokens.begin() + pc.i1);
+            }
+        }
+        j.n_new_segments = (int)(j.result.size() - j.tt_seg0);
+    }
+    S.t_tokts += now_ms() - t_start;
 }
 
 // teacher-forcing hook (FullOpts::spot): the raw logits rows of the spot jobs among `act` (row r of
@@ -2785,6 +2922,7 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
         s->cand_info.push_back(std::move(t->cand_info[j]));
     }
     s->align_ms = std::max(s->align_ms, t->align_ms);
+    s->tokts_ms = std::max(s->tokts_ms, t->tokts_ms);
     s->decoded_tokens += t->decoded_tokens;
     s->pdec_give_ups += t->pdec_give_ups;
     s->pdec_lost_ms += t->pdec_lost_ms;
@@ -2861,6 +2999,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     s->decisions.assign(n_jobs, {});
     s->align_info.assign(n_jobs, {});
     s->align_ms = 0;
+    s->tokts_ms = 0;
     s->decoded_tokens = 0;
     double t0 = now_ms();
     // beams of one clip share its cross K/V cache slot: beam_k > 1 runs in the cache form, with a self slot per beam
@@ -2870,6 +3009,11 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     ensure_ws(c, s, n_jobs * std::max(1, std::max(beam_k, sample_n)), n_jobs);
     compute_mel(c, s, pcm, n, n_jobs, on_device);
     S.t_mel = now_ms() - t0;
+    if (p.token_timestamps) {
+        const double te = now_ms();
+        compute_energy(s, pcm, n, n_jobs, on_device);
+        S.t_tokts += now_ms() - te;
+    }
 
     if (p.temperature_inc > 0.0f && o.fixed_tokens <= 0)
         for (float t = p.temperature; t < 1.0f + 1e-6f; t += p.temperature_inc) S.temps.push_back(t);
@@ -3127,6 +3271,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
         }
         // ---- token timestamps: align every window that just finished with new segments
         if (c->dtw) align_windows(S);
+        // ---- token_timestamps: t0 / t1 / vlen of the new segments' tokens, then the max_len wrap
+        if (p.token_timestamps) token_time_windows(S);
         // ---- new-segment callback (whisper.h single-clip API)
         if (single_api && p.new_segment_callback) {
             Job& j = S.jobs[0];
@@ -3153,6 +3299,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     s->phase_ms[0] = S.t_mel; s->phase_ms[1] = S.t_enc; s->phase_ms[2] = S.t_prefill; s->phase_ms[3] = S.t_decode;
     s->phase_ms[4] = S.t_logits;
     s->align_ms = S.t_align;
+    s->tokts_ms = S.t_tokts;
     std::lock_guard<std::mutex> lk(c->timings_mu);
     c->timings.encode_ms += (float)S.t_enc;
     c->timings.decode_ms += (float)S.t_decode;

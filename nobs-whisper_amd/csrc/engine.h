@@ -139,6 +139,9 @@ struct TokenData {
     int id, tid;
     float p, plog, pt, ptsum;
     int64_t t_dtw = -1;  // 10 ms units; -1 = not aligned (DTW off, a timestamp token, an unaligned window)
+    // whisper_full_params.token_timestamps (token_time_windows): 10 ms units, -1 / 0 when off
+    int64_t t0 = -1, t1 = -1;
+    float vlen = 0.0f;
 };
 
 struct Segment {
@@ -219,6 +222,15 @@ struct Workspace {
     int* al_fr = nullptr;
     char* h_al = nullptr;  // pinned: [cap_jobs AlignClip][cap_jobs * al_rows int]
     int al_cap = 0, al_rows = 0;
+    // token times (whisper_full_params.token_timestamps; allocated by the first call that sets it): the clips'
+    // energy signals, laid out as `pcm` (each clip on a 64-float boundary) and grown like it, the clip descriptors,
+    // and the segment / token lists of one adjust launch (grown on demand)
+    float* energy = nullptr;
+    size_t cap_energy = 0;
+    TtClip* tt_clips = nullptr;
+    TtSeg* tt_segs = nullptr;
+    TtSpan* tt_spans = nullptr;
+    int tt_cap_clips = 0, tt_cap_segs = 0, tt_cap_spans = 0;
 };
 
 struct Job;
@@ -226,7 +238,7 @@ struct Job;
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
-              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_NCLASS };
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 }  // namespace wm
@@ -253,6 +265,7 @@ struct whisper_state {
     std::vector<float> logits_host;
     double phase_ms[5] = {0, 0, 0, 0, 0};
     double align_ms = 0;  // token-timestamp alignment passes of the last call
+    double tokts_ms = 0;  // token_timestamps passes (energy, phase 1, adjust, wrap) of the last call
     // per job of the last call: the cost matrix of its last aligned window (rows x frames f32 on the device,
     // in this state's or its twin's workspace); rows = 0: no window of the job was aligned
     struct AlignInfo { int rows = 0, frames = 0; const float* cost = nullptr; };

@@ -334,6 +334,21 @@ void launch_sample(const float* probs, int n_vocab, const TokOut* in, TokOut* ou
 struct KvCopy;
 void launch_kv_gather(void* cache, int n_slots, int L, int H, int n_ctx, const KvCopy* copies_host, const KvCopy* copies_dev,
                       int n_copies, void* stage, long stage_units, hipStream_t st);
+// ---- token times (kernels/tokts.hip; whisper_full_params.token_timestamps) ---------
+// A clip: its n PCM samples on the device and where its energy signal starts in the energy buffer (floats).
+struct TtClip { const float* pcm; long long e_off; int n, pad; };
+// A segment of n_tok >= 2 tokens of clip `clip`: spans[tok0 .. tok0 + n_tok).
+struct TtSeg { int clip, tok0, n_tok, pad; };
+// A token: t0, t1 in 10 ms units (in / out), is_text = 0 for ids >= eot (left as they are).
+struct TtSpan { long long t0, t1; int is_text, pad; };
+constexpr int kEnergyTile = 1024;  // samples of a clip per workgroup of the energy kernel
+constexpr int kVadChunk = 256;     // samples per round of the adjust kernel's walks
+// energy[clips[c].e_off + i] = (sum_{j=-32..32, inside the clip} |pcm[i + j]|) / 65.0f, the bits of the sequential
+// f32 loop; max_n = the longest clip (the grid). clips: device [n_clips].
+void launch_signal_energy(const TtClip* clips, int n_clips, int max_n, float* energy, hipStream_t st);
+// The voice-activity adjust of every segment's tokens (one workgroup per segment, tokens in order), spans in place.
+// The caller checks the lists (clip indices, token ranges, n >= 1 samples): the kernel trusts them.
+void launch_token_vad(const float* energy, const TtClip* clips, const TtSeg* segs, int n_segs, TtSpan* spans, hipStream_t st);
 // pipelined greedy decoding: advance every row's input token, position and SeqCtl on the device after a step
 // and copy its TokOut (+ the persistent launch's error word, if err) to a ring slot (kernels/logits.hip)
 void launch_decode_advance(int n, int ct, int beg, const TokOut* tout, int* ints, SeqCtl* ctl, TokOut* ring,

@@ -120,6 +120,11 @@ class SeqCtl(C.Structure):
                 ("want_probs", C.c_int32), ("want_nosp", C.c_int32)]
 
 
+class TokenSpan(C.Structure):
+    """struct whisper_mi355x_token_span (include/whisper_mi355x.h): a token of whisper_mi355x_debug_token_vad."""
+    _fields_ = [("t0", C.c_int64), ("t1", C.c_int64), ("is_text", C.c_int32), ("pad", C.c_int32)]
+
+
 BEAM_COMPLETED, BEAM_FAILED, BEAM_WINNER = 1, 2, 4
 
 _lib = None
@@ -197,6 +202,9 @@ def lib() -> C.CDLL:
         "whisper_mi355x_phase_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "whisper_mi355x_align_ms": (C.c_double, [vp]),
         "whisper_mi355x_align_cost": (C.c_int, [vp, C.c_int, fp, C.c_long, ip, ip]),
+        "whisper_mi355x_token_times_ms": (C.c_double, [vp]),
+        "whisper_mi355x_debug_signal_energy": (C.c_int, [vp, fp, ip, C.c_int, fp]),
+        "whisper_mi355x_debug_token_vad": (C.c_int, [vp, fp, ip, C.c_int, ip, ip, C.c_int, C.POINTER(TokenSpan)]),
         "whisper_mi355x_debug_align_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, ip, ip, C.c_int, ip, ip, vp]),
         "whisper_mi355x_debug_align_cost": (C.c_int, [vp, vp, C.c_int, ip, ip, ip, C.c_int, vp]),
         "whisper_mi355x_debug_align_dtw": (C.c_int, [vp, vp, C.c_int, ip, ip, ip, ip, ip]),
@@ -331,6 +339,63 @@ class WhisperContext:
         buf = (C.c_int * 4096)()
         n = self.L.whisper_tokenize(self.ptr, text.encode(), buf, 4096)
         return list(buf[:n])
+
+    def token_str(self, token: int) -> bytes:
+        """whisper_token_to_str: the token's bytes (specials included)."""
+        return self.L.whisper_token_to_str(self.ptr, token) or b""
+
+    @staticmethod
+    def clip_offsets(n_samples) -> list:
+        """Where each clip starts in the concatenated arrays of the two hooks below (the running offset rounded up to
+        64 floats), and the arrays' total length as the last entry."""
+        off = [0]
+        for n in n_samples:
+            off.append(off[-1] + ((int(n) + 63) & ~63))
+        return off
+
+    def debug_signal_energy(self, clips):
+        """whisper_mi355x_debug_signal_energy: the energy signals of the clips (float32 arrays), one launch; a list of
+        arrays, or the negative return code."""
+        import numpy as np
+        ns = [len(x) for x in clips]
+        off = self.clip_offsets(ns)
+        pcm = np.zeros(max(off[-1], 1), np.float32)
+        for x, o in zip(clips, off):
+            pcm[o:o + len(x)] = x
+        out = np.full(max(off[-1], 1), np.nan, np.float32)
+        fp = C.POINTER(C.c_float)
+        rc = self.L.whisper_mi355x_debug_signal_energy(self.ptr, pcm.ctypes.data_as(fp), (C.c_int * len(ns))(*ns), len(ns),
+                                                       out.ctypes.data_as(fp))
+        if rc != 0:
+            return rc
+        return [out[o:o + n].copy() for o, n in zip(off, ns)]
+
+    def debug_token_vad(self, energies, segs):
+        """whisper_mi355x_debug_token_vad: energies = the clips' energy signals; segs = [(clip, [(t0, t1, is_text), ..])].
+        One launch; the adjusted [(t0, t1), ..] per segment, or the negative return code."""
+        import numpy as np
+        ns = [len(x) for x in energies]
+        off = self.clip_offsets(ns)
+        e = np.zeros(max(off[-1], 1), np.float32)
+        for x, o in zip(energies, off):
+            e[o:o + len(x)] = x
+        n_tok = sum(len(t) for _, t in segs)
+        spans = (TokenSpan * max(n_tok, 1))()
+        k = 0
+        for _, toks in segs:
+            for t0, t1, is_text in toks:
+                spans[k] = TokenSpan(int(t0), int(t1), int(bool(is_text)), 0)
+                k += 1
+        rc = self.L.whisper_mi355x_debug_token_vad(self.ptr, e.ctypes.data_as(C.POINTER(C.c_float)), (C.c_int * max(len(ns), 1))(*ns),
+                                                   len(ns), (C.c_int * max(len(segs), 1))(*[c for c, _ in segs]),
+                                                   (C.c_int * max(len(segs), 1))(*[len(t) for _, t in segs]), len(segs), spans)
+        if rc != 0:
+            return rc
+        out, k = [], 0
+        for _, toks in segs:
+            out.append([(spans[k + i].t0, spans[k + i].t1) for i in range(len(toks))])
+            k += len(toks)
+        return out
 
     def close(self):
         # states first, as whisper.h requires (a garbage collector may finalise a context and its
@@ -512,6 +577,23 @@ class WhisperState:
             for t in range(L.whisper_mi355x_batch_segment_n_tokens(self.ptr, job, i)):
                 d = L.whisper_mi355x_batch_token_data(self.ptr, job, i, t)
                 row.append((d.id, d.t_dtw))
+            out.append(row)
+        return out
+
+    def token_times_ms(self) -> float:
+        """Wall time of the token_timestamps passes of the last full / full_batch call (0 when off)."""
+        return float(self.L.whisper_mi355x_token_times_ms(self.ptr))
+
+    def token_data(self, job: int = 0) -> list:
+        """Per segment of the job, per token: the whole whisper_token_data as a dict (id, tid, p, plog, pt, ptsum, t0,
+        t1, t_dtw, vlen). Job 0 is also what whisper_full_get_token_data_from_state returns."""
+        L = self.L
+        out = []
+        for i in range(L.whisper_mi355x_batch_n_segments(self.ptr, job)):
+            row = []
+            for t in range(L.whisper_mi355x_batch_segment_n_tokens(self.ptr, job, i)):
+                d = L.whisper_mi355x_batch_token_data(self.ptr, job, i, t)
+                row.append({f: getattr(d, f) for f, _ in TokenData._fields_})
             out.append(row)
         return out
 
