@@ -182,8 +182,16 @@ WHISPER_API int whisper_mi355x_debug_token_vad(struct whisper_context * ctx, con
 /* Normalised log-mel of the last whisper_pcm_to_mel_with_state / whisper_full_with_state call,
  * copied to host: [n_mel][n_len] f32. Returns n_len. */
 WHISPER_API int whisper_mi355x_get_mel(struct whisper_state * state, float * out, int cap_floats);
-/* Encoder output (ln_post) of window 0 of the last encode, [n_audio_ctx][n_audio_state] f32. */
+/* Encoder output (ln_post) of window 0 of the last encode, [A][n_audio_state] f32; A = the state's audio context
+ * (n_audio_ctx unless whisper_full_params.audio_ctx / whisper_mi355x_set_audio_ctx shortened it). */
 WHISPER_API int whisper_mi355x_get_encoder_out(struct whisper_state * state, float * out, int cap_floats);
+/* The state's audio context (whisper.cpp's exp_n_audio_ctx) for the low-level API: whisper_encode_with_state,
+ * whisper_decode_with_state and whisper_lang_auto_detect_with_state work on the first audio_ctx encoder positions of
+ * a window (the mel window is 2 * audio_ctx frames, zero past it); <= 0 = the model's n_audio_ctx. whisper_full_with_state
+ * stores its params.audio_ctx here after its language detection; a new state, and one from the context's pool, start
+ * at 0. Set it before the encode whose output the decode calls read. Returns 0, -5 when audio_ctx > n_audio_ctx (the
+ * value is then left as it was), -1 for a null state or one whose context was freed. */
+WHISPER_API int whisper_mi355x_set_audio_ctx(struct whisper_state * state, int audio_ctx);
 
 /* Live per-kernel-class timing with HIP events on the state's stream (used by bench.py for the
  * roofline). Classes: 0 encoder-side GEMM (work = FLOPs), 1 encoder attention (FLOPs),

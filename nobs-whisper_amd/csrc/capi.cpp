@@ -275,7 +275,10 @@ int whisper_lang_auto_detect_with_state(struct whisper_context* ctx, struct whis
         if (encode_windows(&ctx->c, s, &job, &seek, &slot, 1) != 0) return -6;
         int tok = v.token_sot, pos = 0, row = 0;
         if (decode_tokens(&ctx->c, s, &tok, &pos, &slot, 1, &row, 1) != 0) return -7;
-        WM_CHECK(hipMemcpy(lg.data(), s->ws.logits + v.token_sot + 1, 100 * 4, hipMemcpyDeviceToHost));
+        // on the state's stream (it does not synchronise with the null stream: a plain hipMemcpy could read the row
+        // before the pass has written it)
+        WM_CHECK(hipMemcpyAsync(lg.data(), s->ws.logits + v.token_sot + 1, 100 * 4, hipMemcpyDeviceToHost, s->stream));
+        WM_CHECK(hipStreamSynchronize(s->stream));
         return 0;
     });
     if (rc != 0) return rc;
@@ -559,7 +562,7 @@ int whisper_mi355x_get_encoder_out(struct whisper_state* s, float* out, int cap)
     return guarded(nullptr, [&]() -> int {
         if (!s || !s->ctx || !s->ws.hn || s->last_enc_windows < 1) return -1;  // orphan state: -1
         Context* c = s->ctx;
-        const long n = (long)c->hp.n_audio_ctx * c->hp.n_audio_state;
+        const long n = (long)enc_ctx(c, s) * c->hp.n_audio_state;
         if (n > cap) return -1;
         hipSetDevice(c->device);
         std::vector<uint16_t> h(n);
@@ -570,6 +573,12 @@ int whisper_mi355x_get_encoder_out(struct whisper_state* s, float* out, int cap)
         }
         return 0;
     });
+}
+int whisper_mi355x_set_audio_ctx(struct whisper_state* s, int audio_ctx) {
+    if (!s || !s->ctx) return -1;  // orphan state: its context was freed
+    if (audio_ctx > s->ctx->hp.n_audio_ctx) return -5;
+    s->audio_ctx = audio_ctx;
+    return 0;
 }
 int whisper_mi355x_state_info(struct whisper_state* s, int out[5]) {
     if (!s || !out) return -1;
@@ -1291,7 +1300,7 @@ int whisper_mi355x_debug_align_scores(struct whisper_context* ctx, const void* q
             if (hl.empty()) continue;
             WM_CHECK(hipMemcpy(dh, hl.data(), hl.size() * sizeof(int2), hipMemcpyHostToDevice));
             launch_align_scores(ctx->c.dt, (const char*)q + (size_t)l * tot * d * 2, d, cross, dcl, n_clips, mr, L, l, H,
-                                hp.n_audio_ctx, dh, (int)hl.size(), P, nullptr);
+                                hp.n_audio_ctx, hp.n_audio_ctx, dh, (int)hl.size(), P, nullptr);
             WM_CHECK(hipDeviceSynchronize());
         }
         hipFree(dh);

@@ -172,6 +172,7 @@ static void reset_for_reuse(whisper_state* s) {
     s->prompt_past.clear();
     s->rng = std::mt19937(0);
     s->lang_id = 0;
+    s->audio_ctx = 0;
     s->n_len = s->n_len_org = 0;
     s->logits_host.clear();
     for (double& t : s->phase_ms) t = 0;
@@ -773,7 +774,10 @@ static LayerMats layer_mats(Context* c, whisper_state* s, bool dec, int l, hipSt
 int encode_windows(Context* c, whisper_state* s, const int* jobs, const int* seeks, const int* slots, int n_win) {
     const Hparams& hp = c->hp;
     Workspace& w = s->ws;
-    const int d = hp.n_audio_state, nm = hp.n_mels, T = hp.n_audio_ctx, H = hp.n_audio_head;
+    // T: the encoder positions of this call (whisper_full_params.audio_ctx). The conv images keep
+    // their 3002-row layout and the cross cache its n_audio_ctx-row planes; hn, qkv, att, ff, x and the direct
+    // form's E hold T rows per window, packed.
+    const int d = hp.n_audio_state, nm = hp.n_mels, T = enc_ctx(c, s), H = hp.n_audio_head;
     const DType dt = c->dt;
     const size_t E = esize(dt);
     const int KCLS = K_GEMM_ENC;
@@ -789,8 +793,9 @@ int encode_windows(Context* c, whisper_state* s, const int* jobs, const int* see
         const int* d_job = w.win_job;
         const int* d_seek = w.win_job + nb;
         const int* d_slot = w.win_job + 2 * nb;
-        launch_mel_window(dt, w.mel_ptrs, w.n_len, w.n_samp, w.mel_max, d_job, d_seek, nb, nm, w.mel_img, st);
-        // conv1 (stride 1, pad 1) + GELU -> h1 rows 1..3000 of each 3002-row image
+        launch_mel_window(dt, w.mel_ptrs, w.n_len, w.n_samp, w.mel_max, d_job, d_seek, nb, nm, 2 * T, w.mel_img, st);
+        // conv1 (stride 1, pad 1) + GELU -> h1 rows 1..2T of each 3002-row image (conv2's last position reads
+        // rows 2T - 2 .. 2T: no row past the ones written here)
         {
             GemmArgs g = gemm_plain(w.mel_img, nb * 2 * T, 3 * nm, W.conv1_w, d, W.conv1_b, w.h1, d);
             g.a_rpb = 2 * T; g.a_bstride = (long)3002 * nm; g.a_rstride = nm;
@@ -848,7 +853,8 @@ int encode_windows(Context* c, whisper_state* s, const int* jobs, const int* see
             // cross K/V of every decoder layer in one GEMM, scattered into each window's slot
             GemmArgs g = gemm_plain(w.hn, M, d, W.wkv_cross, 2 * hp.n_text_layer * d, W.bkv_cross, nullptr, 0);
             g.scale = c->k_scale;
-            g.cache = w.cross; g.row_slot = d_slot; g.L = hp.n_text_layer; g.H = hp.n_text_head; g.ctx = T; g.d = d;
+            g.cache = w.cross; g.row_slot = d_slot; g.L = hp.n_text_layer; g.H = hp.n_text_head; g.ctx = hp.n_audio_ctx; g.d = d;
+            g.rpw = T;
             tgemm(s, KCLS, dt, EPI_CROSSKV, g, st);
             for (int k = 0; k < nb; k++) w.cross_fresh[slots[b0 + k]] = 1;
         }
@@ -869,7 +875,7 @@ static void decoder_upload(Context* c, whisper_state* s, int n_tok, int n_rows, 
     double self_kv = 0;
     for (int i = 0; i < n_tok; i++) {
         hi[3 * ct + i] = hi[ct + i] + 1;
-        hi[4 * ct + i] = hp.n_audio_ctx;
+        hi[4 * ct + i] = enc_ctx(c, s);  // cross keys of the call; rows past them in a slot's planes are an earlier call's
         self_kv += hi[ct + i] + 1;
     }
     s->cur_self_work = self_kv * hp.n_text_head * 64 * 2 * 2;
@@ -1069,6 +1075,7 @@ static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v, bo
     PdecArgs a{};
     a.layers = pdec_layers(c, blocks);
     a.L = L; a.M = n; a.d = d; a.n_text_ctx = hp.n_text_ctx; a.n_audio_ctx = hp.n_audio_ctx;
+    a.n_audio_len = enc_ctx(c, s);
     a.tok_emb = c->w.tok_emb_f32 ? (const void*)c->w.tok_emb_f32 : c->w.tok_emb;
     a.te_f32 = c->w.tok_emb_f32 != nullptr;
     a.pos_d = c->w.pos_d;
@@ -1077,7 +1084,7 @@ static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v, bo
     a.self_cache = w.self; a.cross_cache = w.cross;
     a.k_scale = c->k_scale;
     a.quant = blocks;
-    a.s_cross = pdec_cross_splits(H, hp.n_audio_ctx);
+    a.s_cross = pdec_cross_splits(H, a.n_audio_len);
     a.sync = w.pd_sync;
     a.gr = pdec_granules(d, L, H);
     a.out_dh = (char*)w.dh + (size_t)v.r0 * d * esize(c->dt);
@@ -1086,7 +1093,7 @@ static void decoder_rows_pdec(Context* c, whisper_state* s, const DecView& v, bo
     a.stamps = g_pdec_stamps;
     {
         // weights once + cross K/V + self K/V of every row, per launch
-        const double bytes = 14.0 * d * d * 2 * L + (double)n * L * 2 * hp.n_audio_ctx * d * 2 + s->cur_self_work;
+        const double bytes = 14.0 * d * d * 2 * L + (double)n * L * 2 * a.n_audio_len * d * 2 + s->cur_self_work;
         KT kt(s, K_PDEC, bytes, st);
         launch_pdec(c->dt, a, st);
     }
@@ -1132,7 +1139,7 @@ static void embed_rows(Context* c, const DecRows& r, bool ln) {
 static void xattn_tail(Context* c, whisper_state* s, const DecView& v, const DecRows& r, int l, int step_cls, bool kt_layer) {
     const Weights& W = c->w;
     const DType dt = c->dt;
-    const int d = c->hp.n_text_state, H = c->hp.n_text_head, Ta = c->hp.n_audio_ctx, n = r.n;
+    const int d = c->hp.n_text_state, H = c->hp.n_text_head, Ta = enc_ctx(c, s), n = r.n;  // (E is packed: Ta rows per slot)
     const int S = xattn_splits(n, Ta);
     hipStream_t st = r.st;
     {
@@ -1209,7 +1216,7 @@ static void decoder_rows_small(Context* c, whisper_state* s, const DecView& v, b
         } else {
             small(Lw.qxq, EPI_F32, r.dx, d, Lw.wxq, d, nullptr, raw, d, Lw.lnx_w, Lw.lnx_b);
             const DecSlabs sl{raw, 1, (long)n * d, d, Lw.bxq, c->k_scale};
-            KT kt(s, K_ATTN_CROSS, (double)n * hp.n_audio_ctx * kvrow, st, kt_layer);
+            KT kt(s, K_ATTN_CROSS, (double)n * enc_ctx(c, s) * kvrow, st, kt_layer);
             launch_attn_cross_step(dt, sl, w.cross, r.slot, r.nkv_cross, n, L, l, H, hp.n_audio_ctx, d, r.datt, st);
         }
         small(Lw.qxo, EPI_RESID, r.datt, d, Lw.wxo, d, Lw.bxo, r.dx, d);
@@ -1292,7 +1299,7 @@ static void decoder_rows_step(Context* c, whisper_state* s, const DecView& v, co
             xattn_tail(c, s, v, r, l, K_ATTN_CROSS, kt_layer);
         } else {
             const DecSlabs sl = partials(r.dh, Lw.wxq, d, Lw.bxq, c->k_scale, F.wxq, F.sxq);
-            KT kt(s, K_ATTN_CROSS, (double)n * hp.n_audio_ctx * kvrow, st, kt_layer);
+            KT kt(s, K_ATTN_CROSS, (double)n * enc_ctx(c, s) * kvrow, st, kt_layer);
             launch_attn_cross_step(dt, sl, w.cross, r.slot, r.nkv_cross, n, L, l, H, hp.n_audio_ctx, d, r.datt, st);
         }
         resid(r.datt, d, Lw.wxo, Lw.bxo, Lw.ln2_w, Lw.ln2_b, F.wxo, F.sxo);
@@ -1358,13 +1365,13 @@ static void decoder_rows_prefill(Context* c, whisper_state* s, const DecView& v,
             if (al) {
                 const int k0 = c->dtw_layer_first[l], k1 = c->dtw_layer_first[l + 1];
                 if (k1 > k0) {
-                    KT kt(s, K_ALIGN_SCORES, 2.0 * al->total_rows * hp.n_audio_ctx * 64 * (k1 - k0), st);
+                    KT kt(s, K_ALIGN_SCORES, 2.0 * al->total_rows * enc_ctx(c, s) * 64 * (k1 - k0), st);
                     launch_align_scores(dt, r.dq, d, w.cross, al->clips, al->n_clips, al->max_rows, L, l, H, hp.n_audio_ctx,
-                                        (const int2*)c->dtw_heads_dev + k0, k1 - k0, al->P, st);
+                                        enc_ctx(c, s), (const int2*)c->dtw_heads_dev + k0, k1 - k0, al->P, st);
                 }
                 if (l == c->dtw_last_layer) return;
             }
-            KT kt(s, K_OTHER, (double)n * hp.n_audio_ctx * kvrow, st);
+            KT kt(s, K_OTHER, (double)n * enc_ctx(c, s) * kvrow, st);
             launch_attn_prefill(dt, r.dq, d, w.cross, r.slot, r.nkv_cross, w.qtiles, w.n_qtiles, L, l, H, hp.n_audio_ctx, d, r.datt, st);
         }
         resid(r.datt, d, Lw.wxo, Lw.bxo, Lw.ln2_w, Lw.ln2_b);
@@ -1378,7 +1385,8 @@ static void decoder_rows_prefill(Context* c, whisper_state* s, const DecView& v,
 
 // The two stream halves of a decode step's scratch: group views on the state's stream use the first
 // half of the split-K slabs and cross-attention partials, views on stream2 the second. A group of
-// <= gmax rows uses at most gmax * xattn_splits(gmax) partial rows.
+// <= gmax rows uses at most gmax * xattn_splits(gmax) partial rows; the offset of the second half is the worst
+// case over the audio contexts a call may ask for (xattn_splits grows with its key count: the model's n_audio_ctx).
 static void dec_halves(Context* c, whisper_state* s, int gmax, bool xdirect, DecView& a, DecView& b) {
     Workspace& w = s->ws;
     const int H = c->hp.n_text_head, d = c->hp.n_text_state;
@@ -1431,7 +1439,7 @@ static void decoder_launch(Context* c, whisper_state* s, const StepPlan& P) {
 static void ensure_cross_cache(Context* c, whisper_state* s, const std::vector<int>& slots) {
     Workspace& w = s->ws;
     const Hparams& hp = c->hp;
-    const int d = hp.n_audio_state, T = hp.n_audio_ctx, L = hp.n_text_layer;
+    const int d = hp.n_audio_state, T = enc_ctx(c, s), L = hp.n_text_layer;  // (E: T rows per slot, packed)
     const size_t E = esize(c->dt);
     std::vector<int> stale;
     int need = 0;
@@ -1448,7 +1456,8 @@ static void ensure_cross_cache(Context* c, whisper_state* s, const std::vector<i
         GemmArgs g = gemm_plain((const char*)w.enc + (size_t)sl * T * d * E, k * T, d, c->w.wkv_cross, 2 * L * d,
                                 c->w.bkv_cross, nullptr, 0);
         g.scale = c->k_scale;
-        g.cache = w.cross; g.row_slot = w.kvslot + sl; g.L = L; g.H = hp.n_text_head; g.ctx = T; g.d = d;
+        g.cache = w.cross; g.row_slot = w.kvslot + sl; g.L = L; g.H = hp.n_text_head; g.ctx = hp.n_audio_ctx; g.d = d;
+        g.rpw = T;
         tgemm(s, K_GEMM_ENC, c->dt, EPI_CROSSKV, g, s->stream);
         for (size_t i = a; i < b; i++) w.cross_fresh[stale[i]] = 1;
         a = b;
@@ -1856,7 +1865,7 @@ static void align_windows(Sched& S) {
         j.al_pending = false;
         Item it;
         it.job = k;
-        it.F = std::min(j.al_frames / 2, hp.n_audio_ctx);
+        it.F = std::min(j.al_frames / 2, enc_ctx(c, s));
         it.toks = {v.token_sot};
         if (v.is_multilingual()) it.toks.push_back(v.token_sot + 1 + j.lang_id);
         it.n_sot = (int)it.toks.size();
@@ -2197,10 +2206,11 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     }
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
-            g.par == par && g.beam == beam && (!s->sample_rows || g.seed == s->sample_seed))
+            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && (!s->sample_rows || g.seed == s->sample_seed))
             return &g;
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
     g.seed = s->sample_seed;  // (a kernel argument of the draw below)
+    g.actx = enc_ctx(c, s);
     hipGraph_t graph;
     s->capture_ev = &g.ev;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -2352,7 +2362,7 @@ static long step_variant(Context* c, whisper_state* s, int n) {
     const int pd = pdec_use(c, s, n, s->direct) ? 1 : 0;
     const bool small = n <= small_rows_max(c);  // deliberately coarser than step_plan's test (no w8, no gemm_small_ok)
     const bool wide = !s->direct && n <= attn_cross_wide_max();
-    const int sp = s->direct ? xattn_splits(n, c->hp.n_audio_ctx) : 0;
+    const int sp = s->direct ? xattn_splits(n, enc_ctx(c, s)) : 0;
     const bool lg64 = n <= 64;
     return pd | (long)small << 2 | (long)wide << 3 | (long)sp << 4 | (long)lg64 << 9 | (long)dec_groups(n) << 10;
 }
@@ -2864,6 +2874,10 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
 int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
     if (single_api || n_jobs <= kPairMin) return full_batch_one(c, s, p, pcm, n, n_jobs, on_device, o, single_api);
+    if (p.audio_ctx > c->hp.n_audio_ctx) {  // (before the halves start: one line, not one per half)
+        fprintf(stderr, "whisper_mi355x: audio_ctx is larger than the maximum allowed (%d > %d)\n", p.audio_ctx, c->hp.n_audio_ctx);
+        return -5;
+    }
     WM_CHECK(hipSetDevice(c->device));
     if (!s->twin) s->twin = create_state(c);
     whisper_state* t = s->twin;
@@ -3007,6 +3021,21 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     // (best_of candidates take self slots like beams, but the call keeps its own cross form: the t = 0 attempt's plan
     // is the one it takes with best_of = 1)
     ensure_ws(c, s, n_jobs * std::max(1, std::max(beam_k, sample_n)), n_jobs);
+    // audio_ctx. whisper_full_with_state detects the language before it checks and stores
+    // params.audio_ctx in the state, so the detection pass encodes at the state's earlier value (0 on a fresh state,
+    // and for every clip of the batch API); apply_audio_ctx is that check-and-store, run once after the detection
+    // (or before the first window when there is none).
+    if (!single_api) s->audio_ctx = 0;
+    bool ctx_applied = false;
+    auto apply_audio_ctx = [&]() -> int {
+        ctx_applied = true;
+        if (p.audio_ctx > hp.n_audio_ctx) {
+            fprintf(stderr, "whisper_mi355x: audio_ctx is larger than the maximum allowed (%d > %d)\n", p.audio_ctx, hp.n_audio_ctx);
+            return -5;
+        }
+        s->audio_ctx = p.audio_ctx;
+        return 0;
+    };
     compute_mel(c, s, pcm, n, n_jobs, on_device);
     S.t_mel = now_ms() - t0;
     if (p.token_timestamps) {
@@ -3067,6 +3096,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     };
     for (auto& j : S.jobs)
         if (j.phase != PH_DONE && !j.lang_pending && !build_prompt_init(j)) return -7;
+    if (!need_lang)
+        if (const int r = apply_audio_ctx()) return r;
 
     Workspace& w = s->ws;
     std::vector<std::vector<float>> probs_rows;
@@ -3117,6 +3148,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
             if (!act.empty()) {
                 const double tp = now_ms();
                 const int na = (int)act.size();
+                const int det_ctx = enc_ctx(c, s);
                 int* hi = w.h_ints;
                 for (int r = 0; r < na; r++) {
                     hi[r] = v.token_sot; hi[w.cap_tok + r] = 0; hi[2 * w.cap_tok + r] = S.jobs[act[r]].slot;
@@ -3129,6 +3161,11 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                                             hipMemcpyDeviceToHost, s->stream));
                 WM_CHECK(hipStreamSynchronize(s->stream));
                 S.t_prefill += now_ms() - tp;
+                // (every clip of the call detects in this one pass: need_lang holds for all of them)
+                if (!ctx_applied && !p.detect_language)
+                    if (const int r = apply_audio_ctx()) return r;
+                // window 0 as the detection encoded it serves the first attempt only at the same audio context
+                const bool same_ctx = enc_ctx(c, s) == det_ctx;
                 for (int r = 0; r < na; r++) {
                     Job& j = S.jobs[act[r]];
                     // whisper_lang_auto_detect_with_state: iterate g_lang (std::map, key order), sort desc
@@ -3141,7 +3178,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                     j.lang_pending = false;
                     if (!build_prompt_init(j)) return -7;
                     if (p.detect_language) { j.phase = PH_DONE; continue; }
-                    if (j.seek == 0) {
+                    if (j.seek == 0 && same_ctx) {
                         j.temp_idx = 0;
                         j.phase = PH_PREFILL;
                     } else j.phase = PH_ENCODE;
@@ -3284,6 +3321,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
             }
         }
     }
+    if (!ctx_applied && !p.detect_language)  // (no clip had a window to encode)
+        if (const int r = apply_audio_ctx()) return r;
     for (int k = 0; k < n_jobs; k++) {
         s->results[k] = std::move(S.jobs[k].result);
         s->lang_ids[k] = S.jobs[k].lang_id;

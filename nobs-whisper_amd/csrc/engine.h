@@ -262,6 +262,10 @@ struct whisper_state {
     std::mt19937 rng{0};           // decoder 0's rng: created with the state, never reset
     int lang_id = 0;
     int n_len = 0, n_len_org = 0;  // last mel
+    // whisper_full_params.audio_ctx as the last whisper_full call stored it (or whisper_mi355x_set_audio_ctx): the
+    // encoder positions that encode / decode / language detection on this state work on (wm::enc_ctx); <= 0 = the
+    // model's n_audio_ctx. The caches keep n_audio_ctx as their row stride whatever this says.
+    int audio_ctx = 0;
     std::vector<float> logits_host;
     double phase_ms[5] = {0, 0, 0, 0, 0};
     double align_ms = 0;  // token-timestamp alignment passes of the last call
@@ -292,7 +296,9 @@ struct whisper_state {
     // (beam: 0 for greedy steps; a beam-search step's graph ends with the top-k kernel for beam_k candidates and,
     // with split_slots, reads the rows' self slots from ws.sslot: beam_k | split_slots << 8; a sampled step of best_of
     // candidates ends with the draw kernel over the rows' probs: | 1 << 9, and `seed` = the draw's key)
-    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; };
+    // (actx: the encoder positions of the call, wm::enc_ctx: the cross-attention split counts, grid sizes and the
+    // direct form's slot stride of a captured step depend on it)
+    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
     double cur_self_work = 0;                     // self-attention bytes of the current step
@@ -327,6 +333,8 @@ struct whisper_context {
 };
 
 namespace wm {
+// encoder positions per window of the state's current value (whisper.cpp: exp_n_audio_ctx > 0 ? it : n_audio_ctx)
+inline int enc_ctx(const Context* c, const whisper_state* s) { return s->audio_ctx > 0 ? s->audio_ctx : c->hp.n_audio_ctx; }
 bool load_context(Context* c, const char* path, int device, DType dt, bool load_weights);
 void free_context(Context* c);
 whisper_state* new_state(Context* c);

@@ -10,8 +10,10 @@ namespace wm {
 // ---- mel (kernels/mel.hip) ---------------------------------------------------------------------
 void launch_mel(const float* const* d_pcm, const int* d_n, const void* d_tab, const float* d_filt_t, int n_mel,
                 float* const* d_mel, const int* d_nlen, int* d_max, int n_jobs, int max_frames, hipStream_t st);
+// frames: mel frames of a window (2 * the encoder positions, <= 3000); image rows [0, frames + 2) are written
 void launch_mel_window(DType dt, float* const* d_mel, const int* d_nlen, const int* d_n, const int* d_max,
-                       const int* d_win_job, const int* d_win_seek, int n_win, int n_mel, void* out, hipStream_t st);
+                       const int* d_win_job, const int* d_win_seek, int n_win, int n_mel, int frames, void* out,
+                       hipStream_t st);
 void launch_mel_normalize(const float* d_mel, int nl, int n_samples, const int* d_max, int n_mel, float* out, hipStream_t st);
 // ---- audio front-end (kernels/audio.hip; audio.rs VAD chunking + resampler) ------------------------
 // rms[c][w] (row stride rms_stride >= max_n / (rate/50)) of every 20 ms window, then per clip the
@@ -42,7 +44,7 @@ enum Epi : int {
     EPI_RESID = 2,     // f32 out[orow][n] = v + out[orow][n]            (residual stream, in place)
     EPI_GELU_POS = 3,  // f32 out = gelu_ggml(v) + pos[m % pos_rows][n]   (conv2 + positional emb)
     EPI_F32 = 4,       // f32 out = v                                       (logits)
-    EPI_CROSSKV = 5,   // T scatter into cross cache [slot][L][2][H][ctx][64]; K columns scaled
+    EPI_CROSSKV = 5,   // T scatter into cross cache [slot][L][2][H][ctx][64]; K columns scaled; row m = (window m / rpw, t = m % rpw)
     EPI_QKV_DEC = 6,   // n<d: T q[m][n]*scale ; d<=n<2d: K cache (scaled) ; 2d<=n<3d: V cache
     EPI_GELU_F = 7,    // T out = tanh-GELU by formula in f32 (fp8 mode, and bf16 encoders: not ggml's f16 table)
 };
@@ -72,6 +74,9 @@ struct GemmArgs {
     float scale; int sc_div, sc_mod, sc_lim;           // column n scaled iff ((n/sc_div)%sc_mod) < sc_lim
     // caches (EPI_CROSSKV / EPI_QKV_DEC)
     void* cache; const int* row_slot; const int* row_pos; int L, layer, H, ctx, d;
+    // EPI_CROSSKV: rows of A per window (the call's encoder positions, <= ctx; ctx stays the cache's row stride).
+    // 0 = ctx (launch_gemm fills it in)
+    int rpw;
     // split-K workspace for skinny (decode-step) GEMMs: f32 [splits][M][N]; null disables split-K
     float* splitk_ws; long splitk_ws_elems;
     // EPI_RESID on the split-K path only: fused LayerNorm of the updated residual rows,
@@ -188,10 +193,10 @@ struct AlignClip {
 // Softmaxed score rows of the alignment heads of one decoder layer: heads[k] = {head, index a in the
 // context's head list} (device, n_heads entries); q [rows][q_stride] in the compute type (cross-Q of that
 // layer, already scaled), cross = the cross K/V cache [slot][L][2][H][ctx][64]. P[a][i][t] =
-// softmax_t(q_i . k_t) over all ctx keys in f32, written for t < F only. K is read once per (clip, head).
+// softmax_t(q_i . k_t) over the first n_keys <= ctx keys in f32, written for t < F only. K is read once per (clip, head).
 void launch_align_scores(DType dt, const void* q, int q_stride, const void* cross, const AlignClip* clips, int n_clips,
-                         int max_rows, int L, int layer, int H, int ctx, const int2* heads, int n_heads, float* P,
-                         hipStream_t st);
+                         int max_rows, int L, int layer, int H, int ctx, int n_keys, const int2* heads, int n_heads,
+                         float* P, hipStream_t st);
 // z-score per (head, frame) over the token rows, width-7 median along the frames, head mean, negation,
 // row slice: P -> cost (stats is scratch). max_rows / max_frames: the largest N / F of the clips.
 void launch_align_cost(const float* P, const AlignClip* clips, int n_clips, int A, int max_rows, int max_frames, float* stats,
@@ -260,7 +265,8 @@ __host__ __device__ inline PdecLds pdec_lds(int d, int M, int S) {
 }
 struct PdecArgs {
     const PdecLayer* layers;  // device array [L]
-    int L, M, d, n_text_ctx, n_audio_ctx;
+    int L, M, d, n_text_ctx, n_audio_ctx;  // n_audio_ctx: the cross cache's row stride
+    int n_audio_len;                       // keys per clip of the cross attention (<= n_audio_ctx)
     const void* tok_emb; int te_f32; const float* pos_d;
     const float *lnd_w, *lnd_b;
     const int *tok, *pos, *slot;      // [M]

@@ -17,7 +17,8 @@ namespace wm {
 // One workgroup per (alignment head of this layer, clip): Q [n <= 256][64] stays in registers as MFMA A
 // fragments (wave w owns the 16-row tiles w, w + 4, w + 8, w + 12), the head's K plane [ctx][64] is
 // streamed ONCE through LDS in tiles of 64 keys. Sweep 1 writes the raw f32 scores of the frames t < F
-// and keeps every row's running max and sum over all ctx keys (f32, rescaled when the max moves); sweep 2
+// and keeps every row's running max and sum over the n_keys keys (f32, rescaled when the max moves; ctx is the
+// plane's allocated rows, n_keys <= ctx those of the call's audio context); sweep 2
 // normalises the stored scores in place: P = exp(s - m) / l. Each lane re-reads only what it wrote.
 // Q and K both carry d_head^-0.25, so the product is q.k / 8.
 constexpr int kAlKeys = 64;   // keys per LDS tile
@@ -26,7 +27,7 @@ constexpr int kAlKPad = 72;   // LDS row stride in elements (64 + 16 bytes: the 
 template <typename T>
 __global__ __launch_bounds__(256) void align_scores_kernel(const T* __restrict__ q, int q_stride, const T* __restrict__ cross,
                                                            const AlignClip* __restrict__ clips, int L, int layer, int H, int ctx,
-                                                           const int2* __restrict__ heads, float* __restrict__ P) {
+                                                           int n_keys, const int2* __restrict__ heads, float* __restrict__ P) {
     typedef typename Frag<T>::type F8;
     __shared__ __attribute__((aligned(16))) T Ks[kAlKeys * kAlKPad];
     const AlignClip cl = clips[blockIdx.y];
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void align_scores_kernel(const T* __restrict__
         for (int r = 0; r < 4; r++) { m[i][r] = -INFINITY; l[i][r] = 0.0f; }
     }
 
-    const int n_kt = (ctx + kAlKeys - 1) / kAlKeys;
+    const int n_kt = (n_keys + kAlKeys - 1) / kAlKeys;
     for (int kt = 0; kt < n_kt; kt++) {
         const int k0 = kt * kAlKeys;
         __syncthreads();
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void align_scores_kernel(const T* __restrict__
         for (int u = 0; u < 2; u++) {
             const int c = tid + 256 * u, key = c >> 3, part = c & 7;
             F8 v = {};
-            if (k0 + key < ctx) v = *(const F8*)(K + (size_t)(k0 + key) * 64 + part * 8);
+            if (k0 + key < n_keys) v = *(const F8*)(K + (size_t)(k0 + key) * 64 + part * 8);
             *(F8*)(Ks + key * kAlKPad + part * 8) = v;
         }
         __syncthreads();
@@ -90,13 +91,13 @@ __global__ __launch_bounds__(256) void align_scores_kernel(const T* __restrict__
 #pragma unroll
                 for (int ct = 0; ct < 4; ct++) {
                     const int key = k0 + 16 * ct + lr;
-                    s[ct] = key < ctx ? acc[ct][r] : -INFINITY;
+                    s[ct] = key < n_keys ? acc[ct][r] : -INFINITY;
                     mx = fmaxf(mx, s[ct]);
                     if (r0 + r < n && key < F) Pa[(size_t)(r0 + r) * F + key] = s[ct];
                 }
 #pragma unroll
                 for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-                const float mn = fmaxf(m[i][r], mx);  // finite: every tile holds a key < ctx
+                const float mn = fmaxf(m[i][r], mx);  // finite: every tile holds a key < n_keys
                 float sum = 0.0f;
 #pragma unroll
                 for (int ct = 0; ct < 4; ct++) sum += expf(s[ct] - mn);
@@ -129,17 +130,18 @@ __global__ __launch_bounds__(256) void align_scores_kernel(const T* __restrict__
 }
 
 void launch_align_scores(DType dt, const void* q, int q_stride, const void* cross, const AlignClip* clips, int n_clips,
-                         int max_rows, int L, int layer, int H, int ctx, const int2* heads, int n_heads, float* P,
-                         hipStream_t st) {
+                         int max_rows, int L, int layer, int H, int ctx, int n_keys, const int2* heads, int n_heads,
+                         float* P, hipStream_t st) {
     if (n_clips <= 0 || n_heads <= 0) return;
+    if (n_keys < 1 || n_keys > ctx) WM_FAIL("align scores: %d keys of a %d-row cache plane", n_keys, ctx);
     if (max_rows > 256) WM_FAIL("align scores: %d token rows per clip (at most 256)", max_rows);
     const dim3 grid(n_heads, n_clips);
     if (dt == DType::F16)
         align_scores_kernel<half_t><<<grid, 256, 0, st>>>((const half_t*)q, q_stride, (const half_t*)cross, clips, L, layer, H,
-                                                         ctx, heads, P);
+                                                         ctx, n_keys, heads, P);
     else
         align_scores_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)q, q_stride, (const bf16_t*)cross, clips, L, layer, H,
-                                                         ctx, heads, P);
+                                                         ctx, n_keys, heads, P);
     WM_CHECK(hipGetLastError());
 }
 

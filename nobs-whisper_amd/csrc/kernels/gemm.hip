@@ -122,7 +122,8 @@ __device__ __forceinline__ long cache_index(const GemmArgs& g, long slot, int l,
 // value is multiplied by g.scale first) decoded from n once, then at(g, m) = the element pointer of row m.
 // gemm8p_kernel's whole-row stores keep n over a loop of rows and fold the column part themselves:
 // index(g, 0, 0) + slot * cache_index(g, 1, 0, 0, 0, 0, 0) + 64 t.
-// EPI_CROSSKV: row m = (clip, audio position t); the N columns are [layer][K | V][d], from layer g.layer on.
+// EPI_CROSSKV: row m = (clip m / g.rpw, audio position t = m % g.rpw <= g.ctx); the N columns are [layer][K | V][d],
+// from layer g.layer on.
 template <typename T>
 struct CrossKvDst {
     int l, kv, h, dh;
@@ -131,7 +132,7 @@ struct CrossKvDst {
         : l(g.layer + n / (2 * g.d)), kv((n / g.d) & 1), h((n % g.d) >> 6), dh(n & 63), scaled(kv == 0) {}
     __device__ __forceinline__ long index(const GemmArgs& g, long slot, long t) const { return cache_index(g, slot, l, kv, h, t, dh); }
     __device__ __forceinline__ T* at(const GemmArgs& g, int m) const {
-        const int b = m / g.ctx, t = m % g.ctx;
+        const int b = m / g.rpw, t = m % g.rpw;  // (rows per window: the cache plane keeps g.ctx rows)
         return (T*)g.cache + index(g, g.row_slot[b], t);
     }
 };
@@ -736,7 +737,7 @@ __global__ void __launch_bounds__(512) gemm8p_kernel(const GemmArgs g, const int
                     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
                     T* dst;
                     if constexpr (EPI == EPI_CROSSKV) {
-                        const int bb = m / g.ctx, t = m - bb * g.ctx;
+                        const int bb = m / g.rpw, t = m - bb * g.rpw;
                         dst = (T*)g.cache + (long)g.row_slot[bb] * sstride + colpart + (long)t * 64;
                     } else if (qcol) {
                         dst = c.at(g, m);
@@ -1961,6 +1962,14 @@ void launch_quant_rows_fp8(DType dt, const void* x, long rows, int K, void* q, f
 void launch_gemm(DType dt, int epi, const GemmArgs& g, hipStream_t st) {
     if (g.M <= 0 || g.N <= 0) return;
     if (g.K % 8 != 0 || g.a_rpb <= 0 || g.o_rpb <= 0) WM_FAIL("gemm shape not supported (K=%d)", g.K);
+    if (epi == EPI_CROSSKV) {
+        GemmArgs x = g;
+        if (x.rpw <= 0) x.rpw = x.ctx;
+        if (x.rpw > x.ctx || x.M % x.rpw != 0) WM_FAIL("cross K/V: %d rows in windows of %d (cache planes of %d)", x.M, x.rpw, x.ctx);
+        if (dt == DType::F16) launch_dt<half_t>(epi, x, st);
+        else launch_dt<bf16_t>(epi, x, st);
+        return;
+    }
     if (dt == DType::F16) launch_dt<half_t>(epi, g, st);
     else launch_dt<bf16_t>(epi, g, st);
 }

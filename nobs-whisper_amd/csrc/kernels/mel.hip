@@ -143,11 +143,13 @@ mel_kernel(const float* const* __restrict__ pcm, const int* __restrict__ n_sampl
 // encoder window [seek, seek+3000) of each job into the conv1 input image: f16/bf16, time-major,
 // with one zero frame on each side (conv padding) -> out[b][3002][n_mel]. Frames past n_len are 0
 // (whisper_encode_internal zero-fills them); frames in [n_fft_frames, n_len) carry log10(1e-10).
+// `frames` <= 3000 (a shortened audio context: 2 * audio_ctx): the window is [seek, seek + frames), image rows
+// [0, frames + 2) are written and row frames + 1 is the right zero pad, whatever the clip holds at that frame.
 template <typename T>
 __global__ void mel_window_kernel(float* const* __restrict__ mel, const int* __restrict__ n_len,
                                   const int* __restrict__ n_samples, const int* __restrict__ max_key,
                                   const int* __restrict__ win_job, const int* __restrict__ win_seek,
-                                  int n_mel, T* __restrict__ out) {
+                                  int n_mel, int frames, T* __restrict__ out) {
     const int b = blockIdx.y;
     const int job = win_job[b];
     const int seek = win_seek[b];
@@ -159,12 +161,12 @@ __global__ void mel_window_kernel(float* const* __restrict__ mel, const int* __r
     const float empty = (float)log10(1e-10);
     const float* m = mel[job];
     T* o = out + (size_t)b * 3002 * n_mel;
-    const int total = 3002 * n_mel;
+    const int total = (frames + 2) * n_mel;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int row = i / n_mel, j = i % n_mel;
         float v = 0.0f;
         const int fr = seek + row - 1;
-        if (row > 0 && row < 3001 && fr < nl) {
+        if (row > 0 && row <= frames && fr < nl) {
             float raw = fr < n_fft_frames ? m[(size_t)j * nl + fr] : empty;
             if ((double)raw < mmax) raw = (float)mmax;
             v = (float)(((double)raw + 4.0) / 4.0);
@@ -207,12 +209,14 @@ void launch_mel(const float* const* d_pcm, const int* d_n, const void* d_tab, co
 }
 
 void launch_mel_window(DType dt, float* const* d_mel, const int* d_nlen, const int* d_n, const int* d_max,
-                       const int* d_win_job, const int* d_win_seek, int n_win, int n_mel, void* out, hipStream_t st) {
-    dim3 grid(cdiv(3002 * n_mel, 256 * 8), n_win);
+                       const int* d_win_job, const int* d_win_seek, int n_win, int n_mel, int frames, void* out,
+                       hipStream_t st) {
+    if (frames < 2 || frames > 3000) WM_FAIL("mel window of %d frames", frames);
+    dim3 grid(cdiv((frames + 2) * n_mel, 256 * 8), n_win);
     if (dt == DType::F16)
-        mel_window_kernel<half_t><<<grid, 256, 0, st>>>(d_mel, d_nlen, d_n, d_max, d_win_job, d_win_seek, n_mel, (half_t*)out);
+        mel_window_kernel<half_t><<<grid, 256, 0, st>>>(d_mel, d_nlen, d_n, d_max, d_win_job, d_win_seek, n_mel, frames, (half_t*)out);
     else
-        mel_window_kernel<bf16_t><<<grid, 256, 0, st>>>(d_mel, d_nlen, d_n, d_max, d_win_job, d_win_seek, n_mel, (bf16_t*)out);
+        mel_window_kernel<bf16_t><<<grid, 256, 0, st>>>(d_mel, d_nlen, d_n, d_max, d_win_job, d_win_seek, n_mel, frames, (bf16_t*)out);
 }
 
 void launch_mel_normalize(const float* d_mel, int nl, int n_samples, const int* d_max, int n_mel, float* out, hipStream_t st) {

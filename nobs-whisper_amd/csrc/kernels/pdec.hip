@@ -50,9 +50,9 @@ PdecGranules pdec_granules(int d, int L, int H) {
 
 // at most 8 key splits per (row, head): the split-0 merge reads fewer partials and fewer workgroups poll
 // (measured at 1 clip, caps 6 / 8 / 16 / none: base 191.5 / 188.5 / 192.0 / 195.8 us per step, large-v3
-// unchanged within noise). A function of the model shape only, not of the clip count (round 5, ADVICE r4:
-// a clip's result must not change with the number of clips still decoding): above 256 tasks (large-v3 at
-// 2-4 clips) workgroups take several.
+// unchanged within noise). A function of the model shape and the call's key count (rows: n_audio_ctx, or the
+// call's audio_ctx) only, not of the clip count (round 5, ADVICE r4: a clip's result must not change with the
+// number of clips still decoding): above 256 tasks (large-v3 at 2-4 clips) workgroups take several.
 int pdec_cross_splits(int H, int rows) { return std::max(1, std::min({kG / H, rows / 16, 8})); }
 
 // Zeroes the hand-off block before every launch (gr.bytes is a multiple of 16). A kernel, not hipMemsetAsync: as a
@@ -68,7 +68,8 @@ void launch_pdec(DType dt, const PdecArgs& a, hipStream_t st) {
     if ((long)a.M * (a.d / 64) * a.s_cross * 66 > a.gr.err_bytes / 8 - a.gr.part) WM_FAIL("pdec: split count");
     // self attention in one chunk (16 rows per lane group); cross-attention tasks of at most 1536 rows (the
     // scores buffer)
-    if (a.n_text_ctx > 16 * kNT / 8 || (a.n_audio_ctx + a.s_cross - 1) / a.s_cross > 1536) WM_FAIL("pdec: context sizes");
+    if (a.n_audio_len < 1 || a.n_audio_len > a.n_audio_ctx) WM_FAIL("pdec: %d keys of a %d-row cross cache", a.n_audio_len, a.n_audio_ctx);
+    if (a.n_text_ctx > 16 * kNT / 8 || (a.n_audio_len + a.s_cross - 1) / a.s_cross > 1536) WM_FAIL("pdec: context sizes");
     const PdecLds ll = pdec_lds(a.d, a.M, a.s_cross);
     if (ll.bytes > 160 * 1024) WM_FAIL("pdec: %d bytes of LDS", ll.bytes);
     const size_t lds = ll.bytes;

@@ -47,7 +47,7 @@
 // weights rounded to T before P.V (ggml rounds the normalised P to f16: another rounding point, the
 // same precision), splits merged with exp(m_s - m) in f32 and the result rounded to T (the out
 // projection's src1). A row's results do not depend on the other rows (round 5): the key-split count is a
-// function of the model shape (pdec_cross_splits), the LayerNorm sums run in one order for every M, and the
+// function of the model shape and the call's audio context (pdec_cross_splits), the LayerNorm sums run in one order for every M, and the
 // one-row and four-row builds share every reduction, so a clip decodes the same bits whether 1 or 4 clips
 // share the step (tests/test_gpu_pdec.py::test_pdec_batch_equals_single).
 #pragma once
@@ -832,7 +832,8 @@ __global__ void __launch_bounds__(kNT, 1) pdec_kernel(const PdecArgs a) {
             stamp(l, 3, 1);
         }
         // ---- E: cross attention over the cached K/V, split over keys; split 0 of a (row, head) merges -----------
-        // The split count is a function of the model shape only (pdec_cross_splits): M * H * S tasks, dealt to
+        // The split count is a function of the model shape and the call's key count only (pdec_cross_splits), never
+        // of the row count: M * H * S tasks, dealt to
         // the workgroups round-robin (task t by workgroup t % 256). Every task's attention and publish comes
         // before any merge waits, so no wait can stand behind another workgroup's unfinished task.
         {
@@ -844,11 +845,11 @@ __global__ void __launch_bounds__(kNT, 1) pdec_kernel(const PdecArgs a) {
             };
             const int S = a.s_cross, NT = M * H * S;
             const bool multi = NT > kG;  // (uniform) some workgroups take two or more tasks
-            const int T_ = a.n_audio_ctx;
+            const int T_ = a.n_audio_ctx, TL = a.n_audio_len;  // rows of a cache plane (the stride) / keys of this call
             if (w0 >= NT) ahead();
             for (int t = w0; t < NT; t += kG) {
                 const int m = t / (H * S), h = (t / S) % H, s = t % S;
-                const int r0 = (int)((long)s * T_ / S), r1 = (int)((long)(s + 1) * T_ / S);
+                const int r0 = (int)((long)s * TL / S), r1 = (int)((long)(s + 1) * TL / S);
                 const long sl = SLOT[m];
                 const T* Kc = cross + (((sl * L + l) * 2 + 0) * H + h) * (long)T_ * 64;
                 const T* Vc = cross + (((sl * L + l) * 2 + 1) * H + h) * (long)T_ * 64;

@@ -212,6 +212,7 @@ def lib() -> C.CDLL:
         "whisper_mi355x_get_encoder_out": (C.c_int, [vp, fp, C.c_int]),
         "whisper_mi355x_state_stream": (vp, [vp]),
         "whisper_mi355x_state_info": (C.c_int, [vp, ip]),
+        "whisper_mi355x_set_audio_ctx": (C.c_int, [vp, C.c_int]),
         "whisper_mi355x_weight_arena": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]),
         "whisper_mi355x_rccl_unique_id": (C.c_int, [C.c_char_p]),
         "whisper_mi355x_broadcast_weights": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
@@ -535,6 +536,11 @@ class WhisperState:
     def set_sample_seed(self, seed: int) -> None:
         """whisper_mi355x_set_sample_seed: the key of the device-side draws of sampled candidates (default 0)."""
         self.L.whisper_mi355x_set_sample_seed(self.ptr, seed & 0xFFFFFFFFFFFFFFFF)
+
+    def set_audio_ctx(self, n: int) -> int:
+        """whisper_mi355x_set_audio_ctx: the encoder positions the low-level encode / decode / language-detection
+        calls on this state work on (<= 0: the model's n_audio_ctx). Returns 0, or -5 when n > n_audio_ctx."""
+        return int(self.L.whisper_mi355x_set_audio_ctx(self.ptr, int(n)))
 
     def decisions(self, job: int = 0) -> list:
         """Per-window temperature-fallback decisions of the last full (job 0) / full_batch call."""
