@@ -189,10 +189,8 @@ static void reset_for_reuse(whisper_state* s) {
     s->pdec_lost_ms = 0;
     s->pdec_off_until = 0;
     s->pdec_off = false;
-    s->beam_k = 0;
-    s->split_slots = false;
+    s->mode = StepMode{};
     s->beam_info.clear();
-    s->sample_rows = false;
     s->sample_seed = 0;
     s->cand_info.clear();
     s->gather_rows = s->gather_rows_full = 0;
@@ -293,9 +291,7 @@ void recover_state(whisper_state* s) {
         }
     }
     s->capture_ev = nullptr;
-    s->beam_k = 0;  // (an error inside a beam step)
-    s->split_slots = false;
-    s->sample_rows = false;
+    s->mode = StepMode{};
     hipStreamSynchronize(s->stream);
     hipStreamSynchronize(s->stream2);
     (void)hipGetLastError();
@@ -959,7 +955,7 @@ static bool pdec_blocks(Context* c) {
 // weights are f16 / bf16 or GGML blocks (not the fp8 decoder copies), the device has the 256 CUs the
 // grid is built for, and the step is in the cross K/V cache form.
 static bool pdec_use(Context* c, whisper_state* s, int n, bool xdirect) {
-    if (xdirect || s->pdec_off || s->split_slots || n < 1 || n > pdec_max()) return false;
+    if (xdirect || s->pdec_off || s->mode.split_slots || n < 1 || n > pdec_max()) return false;
     if (dec_fp8(c)) return false;
     // one weight form for every decoder matrix (the kernel is built per form)
     const bool quant = c->w.dec[0].qqkv.type != 0;
@@ -1015,7 +1011,7 @@ static StepPlan step_plan(Context* c, whisper_state* s, int n, bool xdirect, boo
         if (pd) return STEP_PDEC;
         // (beam search with several beams per clip, split_slots: the split-K chain at every row count, so that a
         // beam's bits do not change when other beams complete and the step's rows drop to the small-M range)
-        const bool small = !P.w8 && !s->split_slots && rows <= small_rows_max(c) && gemm_small_ok(rows, d, true) &&
+        const bool small = !P.w8 && !s->mode.split_slots && rows <= small_rows_max(c) && gemm_small_ok(rows, d, true) &&
                            gemm_small_ok(rows, 4 * d, false);
         return small ? STEP_SMALL : STEP_SPLITK;
     };
@@ -1109,7 +1105,7 @@ struct DecRows {
     int n;
     hipStream_t st;
     int *tok, *pos, *slot, *nkv_self, *nkv_cross;
-    int* sslot;  // the rows' self-cache slots: `slot`, or the beams' own slots (whisper_state::split_slots)
+    int* sslot;  // the rows' self-cache slots: `slot`, or the hypotheses' own slots (StepMode::split_slots)
     float* dx;
     void *dh, *dq, *datt, *dff, *qx;
 };
@@ -1117,7 +1113,7 @@ static DecRows dec_rows(Context* c, whisper_state* s, const DecView& v) {
     Workspace& w = s->ws;
     const size_t d = c->hp.n_text_state, H = c->hp.n_text_head, E = esize(c->dt), r0 = v.r0;
     return DecRows{v.n, v.st, w.tok + r0, w.pos + r0, w.slot + r0, w.nkv_self + r0, w.nkv_cross + r0,
-                   (s->split_slots ? w.sslot : w.slot) + r0, w.dx + r0 * d,
+                   (s->mode.split_slots ? w.sslot : w.slot) + r0, w.dx + r0 * d,
                    (char*)w.dh + r0 * d * E, (char*)w.dq + r0 * d * E, (char*)w.datt + r0 * d * E, (char*)w.dff + r0 * 4 * d * E,
                    w.qx ? (void*)((char*)w.qx + r0 * 2 * H * d * E) : nullptr};
 }
@@ -1504,6 +1500,17 @@ int decode_tokens(Context* c, whisper_state* s, const int* tokens, const int* po
 // as best_of candidates drawn on the device, sample_step)
 enum Phase { PH_ENCODE, PH_LANG, PH_PREFILL, PH_DECODE, PH_BEAM, PH_SAMPLE, PH_DONE };
 
+// The decoder state of one hypothesis of an attempt: the clip's one greedy / host-sampled decoder (Job::seq), a beam, a
+// best_of candidate. The per-token code (process_step, fill_ctl, score_seq) takes the clip and the sequence.
+struct Seq {
+    std::vector<TokenData> tokens;
+    int result_len = 0;
+    double sum_logprobs_all = 0, sum_logprobs = -INFINITY, avg_logprobs = -INFINITY, entropy = 0, score = -INFINITY;
+    int seek_delta = 100 * WHISPER_CHUNK_SIZE;
+    bool has_ts = false, failed = false, completed = false;
+    int step = 0;  // index of the last token decoded (advanced by process_step)
+};
+
 struct Job {
     int slot = 0;
     int n_samples = 0, n_len = 0, n_len_org = 0;
@@ -1512,12 +1519,7 @@ struct Job {
     int lang_id = 0;
     std::vector<int> prompt_init, prompt_past, prompt;
     int temp_idx = 0;
-    std::vector<TokenData> tokens;
-    int result_len = 0;
-    double sum_logprobs_all = 0, sum_logprobs = -INFINITY, avg_logprobs = -INFINITY, entropy = 0, score = -INFINITY;
-    int seek_delta = 3000;
-    bool has_ts = false, failed = false, completed = false;
-    int step = 0;
+    Seq seq;  // the attempt's decoder; after a beam or best_of attempt: its winner (hyps_finish)
     float no_speech_prob = 0.0f;
     std::mt19937* rng = nullptr;
     std::mt19937 own_rng{0};
@@ -1538,44 +1540,28 @@ struct Job {
     TtState tt;
 };
 
-// Beam search: a beam is the decoder part of a Job plus its self-cache slot. The per-token code
-// (process_step, fill_ctl, score_seq) works on a Job, so a beam is swapped into its clip's Job around those calls
-// (swap_dec) and out again.
-struct Beam {
-    std::vector<TokenData> tokens;
-    int result_len = 0;
-    double sum_logprobs_all = 0, sum_logprobs = -INFINITY, avg_logprobs = -INFINITY, entropy = 0, score = -INFINITY;
-    int seek_delta = 100 * WHISPER_CHUNK_SIZE;
-    bool has_ts = false, failed = false, completed = false;
-    int step = 0;
+// A hypothesis of a beam attempt or a candidate of a sampled attempt (§12): a sequence, a decoder row
+// per step while it is live, with its own self-cache slot.
+struct Hyp : Seq {
     bool ended = false;  // process_step said stop (completed, failed, or the window's last step)
     int sslot = 0;
     bool live() const { return !ended && !failed && !completed; }
 };
-struct BeamJob {
-    std::vector<Beam> beams;
-    std::vector<std::vector<int>> held;  // per beam: the tokens (prompt included) whose K/V rows its self slot holds
+// the hypotheses of a clip in PH_BEAM or PH_SAMPLE (a clip is in one of them at a time)
+struct Hyps {
+    std::vector<Hyp> h;
+    std::vector<std::vector<int>> held;  // beams only, per beam: the tokens (prompt included) whose K/V rows its self slot holds
+    bool live() const {
+        for (const Hyp& q : h)
+            if (q.live()) return true;
+        return false;
+    }
 };
-static void swap_dec(Job& j, Beam& b) {
-    j.tokens.swap(b.tokens);
-    std::swap(j.result_len, b.result_len);
-    std::swap(j.sum_logprobs_all, b.sum_logprobs_all);
-    std::swap(j.sum_logprobs, b.sum_logprobs);
-    std::swap(j.avg_logprobs, b.avg_logprobs);
-    std::swap(j.entropy, b.entropy);
-    std::swap(j.score, b.score);
-    std::swap(j.seek_delta, b.seek_delta);
-    std::swap(j.has_ts, b.has_ts);
-    std::swap(j.failed, b.failed);
-    std::swap(j.completed, b.completed);
-    std::swap(j.step, b.step);
-}
 
 struct Sched {
-    int beam_k = 0;  // > 0: WHISPER_SAMPLING_BEAM_SEARCH with this many beams (t = 0 attempts)
-    std::vector<BeamJob> bj;
+    int beam_k = 0;    // > 0: WHISPER_SAMPLING_BEAM_SEARCH with this many beams (t = 0 attempts)
     int sample_n = 1;  // > 1: sampled (t > 0) attempts decode this many candidates per clip on the device
-    std::vector<BeamJob> sj;  // their candidates (a candidate is a Beam: decoder state + self slot; `held` is unused)
+    std::vector<Hyps> hyps;  // per clip (when either is on)
     Context* c;
     whisper_state* s;
     whisper_full_params p;
@@ -1592,34 +1578,35 @@ static double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-static void score_seq(const whisper_full_params& p, Job& j) {
-    if (j.result_len == 0) return;
+static void score_seq(const whisper_full_params& p, Seq& q) {
+    if (q.result_len == 0) return;
     double result = 0.0;
-    for (int i = 0; i < j.result_len; ++i) result += j.tokens[i].plog;
-    j.sum_logprobs = result;
-    j.avg_logprobs = result / j.result_len;
-    double penalty = j.result_len;
+    for (int i = 0; i < q.result_len; ++i) result += q.tokens[i].plog;
+    q.sum_logprobs = result;
+    q.avg_logprobs = result / q.result_len;
+    double penalty = q.result_len;
     if (p.length_penalty > 0.0f) penalty = pow((5.0 + penalty) / 6.0, p.length_penalty);
-    j.score = result / penalty;
+    q.score = result / penalty;
     std::map<int, int> counts;
     int cnt = 0;
-    for (int i = std::max(0, j.result_len - 32); i < j.result_len; ++i) { counts[j.tokens[i].id]++; cnt++; }
+    for (int i = std::max(0, q.result_len - 32); i < q.result_len; ++i) { counts[q.tokens[i].id]++; cnt++; }
     double entropy = 0.0;
-    for (auto& kv : counts) { const double q = kv.second / (double)cnt; entropy -= q * log(q); }
-    j.entropy = entropy;
+    for (auto& kv : counts) { const double f = kv.second / (double)cnt; entropy -= f * log(f); }
+    q.entropy = entropy;
+}
+
+// The end of an attempt for a sequence that has not failed: cut to result_len and scored; the entropy rule may fail it
+static void seq_finish(const whisper_full_params& p, Seq& q) {
+    if (q.failed) return;
+    q.tokens.resize(q.result_len);
+    score_seq(p, q);
+    if (q.result_len > 32 && q.entropy < p.entropy_thold) q.failed = true;
 }
 
 static void start_attempt(Sched& S, Job& j) {
     const Vocab& v = S.c->vocab;
     const float t = S.temps[j.temp_idx];
-    j.tokens.clear();
-    j.result_len = 0;
-    j.sum_logprobs_all = 0;
-    j.sum_logprobs = j.avg_logprobs = j.score = -INFINITY;
-    j.entropy = 0;
-    j.seek_delta = 100 * WHISPER_CHUNK_SIZE;
-    j.failed = j.completed = j.has_ts = false;
-    j.step = 0;
+    j.seq = Seq();
     j.prompt.clear();
     if (!j.prompt_past.empty() && t < 0.5f && S.p.n_max_text_ctx > 0) {
         const int n_take = std::min(std::min(S.p.n_max_text_ctx, S.c->hp.n_text_ctx / 2), (int)j.prompt_past.size());
@@ -1634,14 +1621,14 @@ static bool sample_attempt(const Sched& S, const Job& j) {
     return S.sample_n > 1 && j.temp_idx > 0 && S.temps[j.temp_idx] >= 1e-6f;
 }
 
-static void fill_ctl(Sched& S, Job& j, SeqCtl& ctl, bool want_nosp) {
+static void fill_ctl(Sched& S, const Job& j, const Seq& q, SeqCtl& ctl, bool want_nosp) {
     const Vocab& v = S.c->vocab;
     const float t = S.temps[j.temp_idx];
-    ctl.is_initial = j.tokens.empty();
-    ctl.last_ts = j.tokens.size() > 0 && j.tokens.back().id >= v.token_beg;
-    ctl.penult_ts = j.tokens.size() < 2 || j.tokens[j.tokens.size() - 2].id >= v.token_beg;
-    ctl.has_ts = j.has_ts;
-    ctl.seek_delta = j.seek_delta;
+    ctl.is_initial = q.tokens.empty();
+    ctl.last_ts = q.tokens.size() > 0 && q.tokens.back().id >= v.token_beg;
+    ctl.penult_ts = q.tokens.size() < 2 || q.tokens[q.tokens.size() - 2].id >= v.token_beg;
+    ctl.has_ts = q.has_ts;
+    ctl.seek_delta = q.seek_delta;
     ctl.temperature = t;
     ctl.suppress_blank = S.p.suppress_blank;
     ctl.no_timestamps = S.p.no_timestamps;
@@ -1657,10 +1644,10 @@ static void fill_ctl(Sched& S, Job& j, SeqCtl& ctl, bool want_nosp) {
 static void finish_window(Sched& S, Job& j) {
     const Vocab& v = S.c->vocab;
     const whisper_full_params& p = S.p;
-    const int seek_delta = j.seek_delta;
-    const int result_len = j.result_len;
-    const auto& toks = j.tokens;
-    const bool is_no_speech = (j.no_speech_prob > p.no_speech_thold && j.avg_logprobs < p.logprob_thold);
+    const int seek_delta = j.seq.seek_delta;
+    const int result_len = j.seq.result_len;
+    const auto& toks = j.seq.tokens;
+    const bool is_no_speech = (j.no_speech_prob > p.no_speech_thold && j.seq.avg_logprobs < p.logprob_thold);
     std::vector<int> past;
     if (j.prompt.front() == v.token_prev)
         past.insert(past.end(), j.prompt.begin() + 1, j.prompt.end() - j.prompt_init.size());
@@ -1712,23 +1699,22 @@ static void finish_window(Sched& S, Job& j) {
     j.phase = (j.seek + 10 >= j.seek_end) ? PH_DONE : PH_ENCODE;
 }
 
+// The attempt of j.seq is over (a beam or best_of attempt: its winner, already through seq_finish, which then changes
+// nothing: the tokens are cut, and the score and the entropy rule give the same again)
 static void attempt_done(Sched& S, Job& j) {
-    if (!j.failed) {
-        j.tokens.resize(j.result_len);
-        score_seq(S.p, j);
-        if (j.result_len > 32 && j.entropy < S.p.entropy_thold) j.failed = true;
-    }
+    const Seq& q = j.seq;
+    seq_finish(S.p, j.seq);
     if (j.temp_idx == 0) {  // the greedy attempt's outcome (comparable with whisper.cpp bit for bit)
         j.dec = whisper_mi355x_window_decision{};
-        j.dec.failed0 = j.failed;
-        j.dec.logprob_fail0 = j.avg_logprobs < S.p.logprob_thold;
-        j.dec.result_len0 = j.result_len;
-        j.dec.avg_logprob0 = (float)j.avg_logprobs;
-        j.dec.entropy0 = (float)j.entropy;
+        j.dec.failed0 = q.failed;
+        j.dec.logprob_fail0 = q.avg_logprobs < S.p.logprob_thold;
+        j.dec.result_len0 = q.result_len;
+        j.dec.avg_logprob0 = (float)q.avg_logprobs;
+        j.dec.entropy0 = (float)q.entropy;
     }
     bool success = true;
     if (j.temp_idx != (int)S.temps.size() - 1)
-        if (j.failed || j.avg_logprobs < S.p.logprob_thold) success = false;
+        if (q.failed || q.avg_logprobs < S.p.logprob_thold) success = false;
     if (!success) {
         j.temp_idx++;
         j.phase = PH_PREFILL;
@@ -2038,7 +2024,7 @@ static void token_time_windows(Sched& S) {
 }
 
 // teacher-forcing hook (FullOpts::spot): the raw logits rows of the spot jobs among `act` (row r of
-// w.logits belongs to act[r]) for step `step` of each
+// w.logits belongs to act[r]) for step `step` of each: the index of the token that process_step takes from the row
 static void copy_spot_logits(Sched& S, const std::vector<int>& act) {
     if (!S.o.spot_logits || S.o.n_spot <= 0) return;
     Workspace& w = S.s->ws;
@@ -2046,7 +2032,8 @@ static void copy_spot_logits(Sched& S, const std::vector<int>& act) {
     for (int r = 0; r < (int)act.size(); r++)
         for (int k = 0; k < S.o.n_spot; k++)
             if (S.o.spot[k] == act[r]) {
-                const int step = S.jobs[act[r]].step;
+                const Seq& q = S.jobs[act[r]].seq;
+                const int step = q.tokens.empty() ? 0 : q.step + 1;
                 if (step < 0 || step >= S.o.fixed_tokens) continue;
                 WM_CHECK(hipMemcpyAsync(S.o.spot_logits + ((size_t)step * S.o.n_spot + k) * V, w.logits + (size_t)r * V,
                                         V * 4, hipMemcpyDeviceToHost, S.s->stream));
@@ -2054,12 +2041,15 @@ static void copy_spot_logits(Sched& S, const std::vector<int>& act) {
     WM_CHECK(hipStreamSynchronize(S.s->stream));
 }
 
-// one whisper_full "sample + update" iteration for token index j.step; returns true if decoding continues
+// One whisper_full "sample + update" iteration: the record r of a step's row applied to sequence q of clip j; returns
+// true if decoding continues. The one place that advances q.step: the first token of an attempt (the prefill row's) has
+// index 0, every later one the next index.
 // (drawn: r is the record of a token drawn on the device, launch_sample, which applied the sampled branch's rules)
-static bool process_step(Sched& S, Job& j, const TokOut& r, const float* probs_row, bool drawn = false) {
+static bool process_step(Sched& S, const Job& j, Seq& q, const TokOut& r, const float* probs_row, bool drawn = false) {
     const Vocab& v = S.c->vocab;
     const whisper_full_params& p = S.p;
-    const int i = j.step;
+    if (!q.tokens.empty()) q.step++;
+    const int i = q.step;
     const float t = S.temps[j.temp_idx];
     TokenData td;
     td.tid = r.tid; td.pt = r.pt; td.ptsum = r.ptsum;
@@ -2075,40 +2065,40 @@ static bool process_step(Sched& S, Job& j, const TokOut& r, const float* probs_r
         else { td.tid = r.tid; td.pt = r.pt; }
     }
     if (S.o.forced && S.o.fixed_tokens > 0) td.id = S.o.forced[(long)j.slot * S.o.fixed_tokens + i];
-    j.tokens.push_back(td);
-    j.sum_logprobs_all += td.plog;
+    q.tokens.push_back(td);
+    q.sum_logprobs_all += td.plog;
     S.decoded++;
     const int delta_min = 10;
     if (td.id > v.token_beg) {
         const int sd_new = 2 * (td.id - v.token_beg);
-        if (j.has_ts && j.seek_delta > sd_new && j.result_len < i && S.o.fixed_tokens <= 0) {
-            j.failed = true;
+        if (q.has_ts && q.seek_delta > sd_new && q.result_len < i && S.o.fixed_tokens <= 0) {
+            q.failed = true;
             return false;
         }
-        j.seek_delta = sd_new;
-        j.result_len = i + 1;
-        j.has_ts = true;
+        q.seek_delta = sd_new;
+        q.result_len = i + 1;
+        q.has_ts = true;
     }
     if (S.o.fixed_tokens > 0) {
         if (i == S.n_max_steps - 1) {  // fixed-work mode: one full window per chunk
-            j.result_len = S.n_max_steps;
-            j.seek_delta = 100 * WHISPER_CHUNK_SIZE;
-            j.completed = true;
+            q.result_len = S.n_max_steps;
+            q.seek_delta = 100 * WHISPER_CHUNK_SIZE;
+            q.completed = true;
             return false;
         }
     } else if (td.id == v.token_eot || (p.max_tokens > 0 && i >= p.max_tokens) ||
-               (j.has_ts && j.seek + j.seek_delta + delta_min >= j.seek_end)) {
-        if (j.result_len == 0 && !p.no_timestamps) {
-            if (j.seek + j.seek_delta + delta_min >= j.seek_end) j.result_len = i + 1;
-            else { j.failed = true; return false; }
+               (q.has_ts && j.seek + q.seek_delta + delta_min >= j.seek_end)) {
+        if (q.result_len == 0 && !p.no_timestamps) {
+            if (j.seek + q.seek_delta + delta_min >= j.seek_end) q.result_len = i + 1;
+            else { q.failed = true; return false; }
         }
-        if (p.single_segment || p.no_timestamps) { j.result_len = i + 1; j.seek_delta = 100 * WHISPER_CHUNK_SIZE; }
-        j.completed = true;
+        if (p.single_segment || p.no_timestamps) { q.result_len = i + 1; q.seek_delta = 100 * WHISPER_CHUNK_SIZE; }
+        q.completed = true;
         return false;
     }
     if (S.o.fixed_tokens <= 0 && i == S.n_max_steps - 1 &&
-        (j.result_len == 0 || j.seek_delta < 100 * WHISPER_CHUNK_SIZE / 2)) {
-        j.failed = true;
+        (q.result_len == 0 || q.seek_delta < 100 * WHISPER_CHUNK_SIZE / 2)) {
+        q.failed = true;
         return false;
     }
     // whisper.cpp's loop runs i < n_max: after the last iteration nothing more is sampled (its
@@ -2117,23 +2107,35 @@ static bool process_step(Sched& S, Job& j, const TokOut& r, const float* probs_r
     return true;
 }
 
-// logits kernel over the rows of `act` jobs (row r of w.logits belongs to act[r]) + D2H
-static bool logits_prepare(Sched& S, const std::vector<int>& act, bool want_nosp) {
-    Workspace& w = S.s->ws;
-    const int n = (int)act.size();
-    bool any_probs = false;
-    for (int r = 0; r < n; r++) {
-        fill_ctl(S, S.jobs[act[r]], w.h_ctl[r], want_nosp);
-        any_probs |= w.h_ctl[r].want_probs != 0;
+// A step mode held for one step, also when an error unwinds. A mode with split slots runs in the cache form, whatever
+// the call's cross form is (best_of candidates in a direct-form call): `direct` comes back with the mode's end.
+struct ModeScope {
+    whisper_state* s;
+    const bool direct;
+    ModeScope(whisper_state* s_, StepMode m) : s(s_), direct(s_->direct) {
+        s->mode = m;
+        if (m.split_slots) s->direct = false;
     }
+    ~ModeScope() {
+        s->mode = StepMode{};
+        s->direct = direct;
+    }
+    ModeScope(const ModeScope&) = delete;
+};
+
+// the SeqCtl of the first n staged rows to the device; true if a row wants its probs
+static bool ctl_upload(Sched& S, int n) {
+    Workspace& w = S.s->ws;
+    bool any_probs = false;
+    for (int r = 0; r < n; r++) any_probs |= w.h_ctl[r].want_probs != 0;
     WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, S.s->stream));
     return any_probs;
 }
 static void logits_launch(Context* c, whisper_state* s, int n) {
     Workspace& w = s->ws;
-    if (s->beam_k > 0) {  // a beam step: top-k candidates per row (candidate 0 = the greedy record of the row)
+    if (s->mode.topk > 0) {  // a beam step: top-k candidates per row (candidate 0 = the greedy record of the row)
         KT kt(s, K_TOPK, (double)n * c->hp.n_vocab * 4);
-        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->beam_k, w.lrec, s->stream);
+        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->mode.topk, w.lrec, s->stream);
         return;
     }
     KT kt(s, K_LOGITS, (double)n * c->hp.n_vocab * 4);
@@ -2143,7 +2145,7 @@ static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vect
     Context* c = S.c;
     Workspace& w = S.s->ws;
     hipStream_t st = S.s->stream;
-    if (S.s->beam_k > 0) {
+    if (S.s->mode.topk > 0) {
         WM_CHECK(hipMemcpyAsync(w.h_cand, w.cand, (size_t)n * kTopkMax * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         probs_rows.assign(n, {});
         WM_CHECK(hipStreamSynchronize(st));
@@ -2161,10 +2163,13 @@ static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vect
     }
     WM_CHECK(hipStreamSynchronize(st));
 }
-static void run_logits(Sched& S, const std::vector<int>& act, bool want_nosp, std::vector<std::vector<float>>& probs_rows) {
-    const bool any = logits_prepare(S, act, want_nosp);
-    logits_launch(S.c, S.s, (int)act.size());
-    logits_finish(S, (int)act.size(), any, probs_rows);
+// logits kernel over the prefill rows of the `act` jobs (row r of w.logits belongs to act[r]) + D2H
+static void prefill_logits(Sched& S, const std::vector<int>& act, std::vector<std::vector<float>>& probs_rows) {
+    const int n = (int)act.size();
+    for (int r = 0; r < n; r++) fill_ctl(S, S.jobs[act[r]], S.jobs[act[r]].seq, S.s->ws.h_ctl[r], true);
+    const bool any = ctl_upload(S, n);
+    logits_launch(S.c, S.s, n);
+    logits_finish(S, n, any, probs_rows);
 }
 
 // One decode step (decoder over n active clips + logits kernel) as a replayed hipGraph: the host
@@ -2190,7 +2195,7 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     const int n = P.n, pd = P.path == STEP_PDEC;
     P.pipe = par > 0;
     const int sig = dec_path_sig();
-    const int beam = s->beam_k | (s->split_slots ? 1 << 8 : 0) | (s->sample_rows ? 1 << 9 : 0);
+    const int beam = s->mode.key();
     // read once: a setter stores its value before it bumps the generation, so a graph captured below under
     // generation `gen` holds that generation's (or a newer) stamps pointer and spin limit, and is retired later
     const int gen = g_pdec_gen.load(std::memory_order_acquire);
@@ -2206,7 +2211,7 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     }
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
-            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && (!s->sample_rows || g.seed == s->sample_seed))
+            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && (!s->mode.sample || g.seed == s->sample_seed))
             return &g;
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
     g.seed = s->sample_seed;  // (a kernel argument of the draw below)
@@ -2216,7 +2221,7 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
     decoder_launch(c, s, P);
     logits_launch(c, s, n);
-    if (s->sample_rows) {  // the rows' tokens drawn from their probs, the TokOut records rewritten in place
+    if (s->mode.sample) {  // the rows' tokens drawn from their probs, the TokOut records rewritten in place
         Workspace& w = s->ws;
         KT kt(s, K_SAMPLE, (double)n * c->hp.n_vocab * 4 * 2);
         launch_sample(w.probs, c->hp.n_vocab, w.tout, w.tout, w.sctr, nullptr, s->sample_seed, c->vid.beg, n, s->stream);
@@ -2293,32 +2298,25 @@ static void rerun_given_up(Sched& S, int n, bool any_probs, std::vector<std::vec
     s->pdec_lost_ms += now_ms() - t0;
 }
 
-static void decode_step(Sched& S, const std::vector<int>& act, std::vector<std::vector<float>>& probs_rows) {
+// The staged step of n rows (step_upload) through the par-0 graph of its plan, and its records on the host
+// (logits_finish: w.h_tout and the wanted probs rows, or w.h_cand in the top-k mode).
+static void run_step(Sched& S, int n, bool any_probs, std::vector<std::vector<float>>& probs_rows) {
     Context* c = S.c;
     whisper_state* s = S.s;
-    const int n = (int)act.size();
-    decoder_upload(c, s, n, n, false);
-    const bool any = logits_prepare(S, act, false);
     const double t_step = now_ms();
     whisper_state::DecGraph* G = dec_graph(c, s, dec_path_prepare(c, s, n), 0);
-    if (!G->pdec) {
-        WM_CHECK(hipGraphLaunch(G->exec, s->stream));
-        logits_finish(S, n, any, probs_rows);
-        kt_flush_graph(s, *G);
-        return;
-    }
     // A persistent launch needs its 256 workgroups resident together: persistent steps of different states
     // (threads) of this process on one device never overlap, so two of them cannot hold half the CUs each
     // (steps on different devices do not wait for each other)
     bool gave_up;
     {
-        PdecRunLock lk(c->device);
+        PdecRunLock lk(c->device, G->pdec != 0);
         WM_CHECK(hipGraphLaunch(G->exec, s->stream));
-        logits_finish(S, n, any, probs_rows);
-        gave_up = *s->ws.h_pd_err != 0;
+        logits_finish(S, n, any_probs, probs_rows);
+        gave_up = G->pdec && *s->ws.h_pd_err != 0;
     }
     kt_flush_graph(s, *G);
-    if (gave_up) rerun_given_up(S, n, any, probs_rows, t_step);
+    if (gave_up) rerun_given_up(S, n, any_probs, probs_rows, t_step);
 }
 
 // Pipelined greedy decoding. The per-step path waits for a step's 32-byte results before it launches the next
@@ -2348,7 +2346,7 @@ static bool pipe_ok(Sched& S, const std::vector<int>& act) {
         const Job& j = S.jobs[k];
         if (j.phase == PH_DONE) continue;
         if (j.phase != PH_DECODE) return false;
-        if (S.temps[j.temp_idx] >= 1e-6f || j.step < pipe_min_step()) return false;
+        if (S.temps[j.temp_idx] >= 1e-6f || j.seq.step < pipe_min_step()) return false;
     }
     return !act.empty();
 }
@@ -2367,17 +2365,43 @@ static long step_variant(Context* c, whisper_state* s, int n) {
     return pd | (long)small << 2 | (long)wide << 3 | (long)sp << 4 | (long)lg64 << 9 | (long)dec_groups(n) << 10;
 }
 
-// the host inputs of a decode step of the `act` jobs (their next token, position, slot, logits row)
-static void step_inputs(Sched& S, const std::vector<int>& act) {
+// token `tok` at position `pos` of the clip in `slot` as row i of the decoder's host staging
+static void stage_token(Workspace& w, int i, int tok, int pos, int slot) {
+    w.h_ints[i] = tok; w.h_ints[w.cap_tok + i] = pos; w.h_ints[2 * w.cap_tok + i] = slot;
+}
+
+// Row r of a decode step's host staging: sequence q of clip j decodes its last token (the row's own logits row), with
+// its self-cache rows in slot `sslot` (the clip's own slot, or a hypothesis's) and its logits-rule inputs
+static void stage_row(Sched& S, const Job& j, const Seq& q, int sslot, int r) {
     Workspace& w = S.s->ws;
-    int* hi = w.h_ints;
-    for (int r = 0; r < (int)act.size(); r++) {
-        const Job& j = S.jobs[act[r]];
-        hi[r] = j.tokens.back().id;
-        hi[w.cap_tok + r] = (int)j.prompt.size() + j.step;
-        hi[2 * w.cap_tok + r] = j.slot;
-        hi[5 * w.cap_tok + r] = r;
-    }
+    stage_token(w, r, q.tokens.back().id, (int)j.prompt.size() + q.step, j.slot);
+    w.h_ints[5 * w.cap_tok + r] = r;
+    w.h_sslot[r] = sslot;
+    fill_ctl(S, j, q, w.h_ctl[r], false);
+}
+
+// the n staged rows to the device (the self slots and the draw counters where the step's mode reads them); true if a
+// row wants its probs
+static bool step_upload(Sched& S, int n) {
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    decoder_upload(S.c, s, n, n, false);
+    if (s->mode.split_slots) WM_CHECK(hipMemcpyAsync(w.sslot, w.h_sslot, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    const bool any_probs = ctl_upload(S, n);
+    if (s->mode.sample) WM_CHECK(hipMemcpyAsync(w.sctr, w.h_sctr, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    return any_probs;
+}
+
+// the inputs of a greedy / host-sampled decode step of the `act` jobs, staged and on the device
+static bool step_inputs(Sched& S, const std::vector<int>& act) {
+    for (int r = 0; r < (int)act.size(); r++) stage_row(S, S.jobs[act[r]], S.jobs[act[r]].seq, S.jobs[act[r]].slot, r);
+    return step_upload(S, (int)act.size());
+}
+
+// one decode step of the `act` jobs on the per-step path; row r of w.h_tout and probs_rows belongs to act[r]
+static void decode_step(Sched& S, const std::vector<int>& act, std::vector<std::vector<float>>& probs_rows) {
+    const bool any_probs = step_inputs(S, act);
+    run_step(S, (int)act.size(), any_probs, probs_rows);
 }
 
 // A pipelined step of the `act` rows gave up: the device's inputs again from the host's (the graphs' own
@@ -2386,8 +2410,6 @@ static void pipe_give_up(Sched& S, const std::vector<int>& act, double t0) {
     const int n = (int)act.size();
     WM_CHECK(hipStreamSynchronize(S.s->stream));
     step_inputs(S, act);
-    decoder_upload(S.c, S.s, n, n, false);
-    logits_prepare(S, act, false);
     std::vector<std::vector<float>> probs_rows;
     rerun_given_up(S, n, false, probs_rows, t0);
 }
@@ -2412,8 +2434,6 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
     for (auto& e : w.ring_ev)
         if (!e) WM_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     step_inputs(S, act);
-    decoder_upload(c, s, n, n, false);
-    logits_prepare(S, act, false);
     const StepPlan P = dec_path_prepare(c, s, n);
     const int pd = P.path == STEP_PDEC;
     dec_graph(c, s, P, 1);
@@ -2434,8 +2454,8 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
         bool more = false, fits = true;
         for (int r = 0; r < n; r++) {
             const Job& j = S.jobs[act[r]];
-            more |= j.step + 2 < S.n_max_steps;
-            fits &= (int)j.prompt.size() + j.step + 1 < c->hp.n_text_ctx;
+            more |= j.seq.step + 2 < S.n_max_steps;
+            fits &= (int)j.prompt.size() + j.seq.step + 1 < c->hp.n_text_ctx;
         }
         more = more && fits;
         if (more) {
@@ -2449,18 +2469,16 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
         if (pd && *(const unsigned*)(hslot + (size_t)w.cap_jobs * sizeof(TokOut))) {
             // step k gave up: re-run it on the per-kernel path from the host's inputs, then leave
             pipe_give_up(S, act, t_step);
-            for (int r = 0; r < n; r++) S.jobs[act[r]].step++;
             for (int r = 0; r < n; r++) {
                 Job& j = S.jobs[act[r]];
-                if (!process_step(S, j, w.h_tout[r], nullptr)) attempt_done(S, j);
+                if (!process_step(S, j, j.seq, w.h_tout[r], nullptr)) attempt_done(S, j);
             }
             return false;
         }
-        for (int r = 0; r < n; r++) S.jobs[act[r]].step++;
         bool ended = false;
         for (int r = 0; r < n; r++) {
             Job& j = S.jobs[act[r]];
-            if (!process_step(S, j, out[r], nullptr)) {
+            if (!process_step(S, j, j.seq, out[r], nullptr)) {
                 attempt_done(S, j);
                 ended = true;
             }
@@ -2496,8 +2514,7 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
             }
             for (int r : still) {
                 Job& j = S.jobs[act[r]];
-                j.step++;
-                if (!process_step(S, j, w.h_tout[r], nullptr)) attempt_done(S, j);
+                if (!process_step(S, j, j.seq, w.h_tout[r], nullptr)) attempt_done(S, j);
             }
         }
         return aborted;
@@ -2537,37 +2554,33 @@ static BeamCand to_cand(const TokOut& t) {
 // to `copies`.
 static void beam_reparent(Sched& S, int k, const std::vector<int>& rows, const TokOut* cands, const std::vector<int>& positions,
                           bool first, std::vector<KvCopy>& copies) {
-    Job& j = S.jobs[k];
-    BeamJob& B = S.bj[k];
+    const Job& j = S.jobs[k];
+    Hyps& B = S.hyps[k];
     const int K = S.beam_k;
     std::vector<BeamCand> bc(rows.size() * K);
     std::vector<double> sums(rows.size());
     for (size_t r = 0; r < rows.size(); r++) {
-        sums[r] = first ? 0.0 : B.beams[rows[r]].sum_logprobs_all;
+        sums[r] = first ? 0.0 : B.h[rows[r]].sum_logprobs_all;
         for (int q = 0; q < K; q++) bc[r * K + q] = to_cand(cands[r * kTopkMax + q]);
     }
     const std::vector<BeamPick> picks = beam_select(rows, sums, bc.data(), K, positions);
     std::vector<int> slots;
-    for (const Beam& b : B.beams) slots.push_back(b.sslot);
+    for (const Hyp& b : B.h) slots.push_back(b.sslot);
     const std::vector<KvCopy> cp = beam_copies(picks, B.held, slots);
     for (const KvCopy& x : cp) {
         S.s->gather_rows += x.row1 - x.row0;
         S.s->gather_rows_full += x.row1;
     }
     copies.insert(copies.end(), cp.begin(), cp.end());
-    const std::vector<Beam> old = B.beams;
+    const std::vector<Hyp> old = B.h;
     for (const BeamPick& pk : picks) {
-        Beam& b = B.beams[pk.beam];
+        Hyp& b = B.h[pk.beam];
         if (pk.parent < 0) { b.failed = true; continue; }
         const int sl = b.sslot;
         b = old[pk.parent];
         b.sslot = sl;
-        if (!first) b.step++;
         const size_t r = std::find(rows.begin(), rows.end(), pk.parent) - rows.begin();
-        swap_dec(j, b);
-        const bool more = process_step(S, j, cands[r * kTopkMax + pk.rank], nullptr);
-        swap_dec(j, b);
-        b.ended = !more;
+        b.ended = !process_step(S, j, b, cands[r * kTopkMax + pk.rank], nullptr);
     }
 }
 
@@ -2601,110 +2614,79 @@ static void beam_gather(Sched& S, std::vector<KvCopy>& copies) {
 
 // Contract point 4: the beams of job k start from the candidates of its prefill row (rank r to beam r)
 static void beam_start(Sched& S, int k, const TokOut* cands, std::vector<KvCopy>& copies) {
-    Job& j = S.jobs[k];
-    BeamJob& B = S.bj[k];
+    const Job& j = S.jobs[k];
+    Hyps& B = S.hyps[k];
     const int K = S.beam_k, n_jobs = (int)S.jobs.size();
-    B.beams.assign(K, Beam());
+    B.h.assign(K, Hyp());
     B.held.assign(K, {});
     B.held[0] = j.prompt;  // the prefill wrote the prompt's rows into the clip's own slot
     std::vector<int> positions;
     for (int b = 0; b < K; b++) {
-        B.beams[b].sslot = b * n_jobs + j.slot;
+        B.h[b].sslot = b * n_jobs + j.slot;
         positions.push_back(b);
     }
     beam_reparent(S, k, {0}, cands, positions, true, copies);
 }
 
-// Contract point 6: score the beams, pick the winner, hand it to the Job and to attempt_done
-static void beam_finish(Sched& S, int k) {
+// The end of a beam attempt (contract point 6) or of a best_of attempt of job k: its hypotheses scored as attempt_done
+// scores a single decoder's sequence, the winner (beam_winner) moved into the Job (none: the attempt failed), the
+// hypotheses recorded in `info` (beam_info[k] or cand_info[k]), and on to attempt_done
+static void hyps_finish(Sched& S, int k, std::vector<Hyp>& hyps, std::vector<whisper_state::BeamRec>& info) {
     Job& j = S.jobs[k];
-    BeamJob& B = S.bj[k];
-    const int K = S.beam_k;
+    const int K = (int)hyps.size();
     std::vector<double> score(K);
     std::vector<char> failed(K);
     std::vector<whisper_state::BeamRec> recs(K);
     for (int b = 0; b < K; b++) {
-        Beam& bm = B.beams[b];
-        for (const TokenData& t : bm.tokens) recs[b].tokens.push_back(t.id);
-        recs[b].sum_logprobs_all = bm.sum_logprobs_all;
-        if (!bm.failed) {  // as attempt_done scores a greedy attempt
-            swap_dec(j, bm);
-            j.tokens.resize(j.result_len);
-            score_seq(S.p, j);
-            if (j.result_len > 32 && j.entropy < S.p.entropy_thold) j.failed = true;
-            swap_dec(j, bm);
-        }
-        score[b] = bm.score;
-        failed[b] = bm.failed;
-        recs[b].flags = (bm.completed ? 1 : 0) | (bm.failed ? 2 : 0);
+        Hyp& q = hyps[b];
+        for (const TokenData& t : q.tokens) recs[b].tokens.push_back(t.id);
+        recs[b].sum_logprobs_all = q.sum_logprobs_all;
+        seq_finish(S.p, q);
+        score[b] = q.score;
+        failed[b] = q.failed;
+        recs[b].flags = (q.completed ? 1 : 0) | (q.failed ? 2 : 0);
     }
     const int win = beam_winner(score, failed);
     if (win >= 0) {
         recs[win].flags |= 4;
-        swap_dec(j, B.beams[win]);
+        j.seq = std::move(static_cast<Seq&>(hyps[win]));
     } else {
-        j.failed = true;
+        j.seq.failed = true;
     }
-    S.s->beam_info[k] = std::move(recs);
-    B.beams.clear();
+    info = std::move(recs);
+    hyps.clear();
     attempt_done(S, j);
+}
+
+// The rows of a step of the `jobs` clips' live hypotheses, staged in job order: {job, hypothesis} of every row
+// (`what`, max_rows: the row-limit message)
+static std::vector<std::pair<int, int>> stage_hyps(Sched& S, const std::vector<int>& jobs, const char* what, int max_rows) {
+    std::vector<std::pair<int, int>> rows;
+    for (int k : jobs) {
+        const std::vector<Hyp>& h = S.hyps[k].h;
+        for (int b = 0; b < (int)h.size(); b++) {
+            if (!h[b].live()) continue;
+            if ((int)rows.size() >= max_rows) WM_FAIL("%s: more than %d rows in a step", what, max_rows);
+            stage_row(S, S.jobs[k], h[b], h[b].sslot, (int)rows.size());
+            rows.push_back({k, b});
+        }
+    }
+    return rows;
 }
 
 // One decode step of every live beam of the `bjobs` clips (all in PH_BEAM), then the re-parenting of each clip
 static void beam_step(Sched& S, const std::vector<int>& bjobs) {
-    Context* c = S.c;
-    whisper_state* s = S.s;
-    Workspace& w = s->ws;
+    Workspace& w = S.s->ws;
     const int K = S.beam_k;
-    int* hi = w.h_ints;
-    std::vector<std::pair<int, int>> rows;  // {job, beam}
-    for (int k : bjobs) {
-        Job& j = S.jobs[k];
-        BeamJob& B = S.bj[k];
-        for (int b = 0; b < K; b++) {
-            Beam& bm = B.beams[b];
-            if (!bm.live()) continue;
-            const int r = (int)rows.size();
-            if (r >= w.cap_jobs) WM_FAIL("beam search: more than %d rows in a step", w.cap_jobs);
-            hi[r] = bm.tokens.back().id;
-            hi[w.cap_tok + r] = (int)j.prompt.size() + bm.step;
-            hi[2 * w.cap_tok + r] = j.slot;
-            hi[5 * w.cap_tok + r] = r;
-            w.h_sslot[r] = bm.sslot;
-            B.held[b].push_back(bm.tokens.back().id);  // this step writes the token's K/V row into the beam's slot
-            swap_dec(j, bm);
-            fill_ctl(S, j, w.h_ctl[r], false);
-            swap_dec(j, bm);
-            rows.push_back({k, b});
-        }
-    }
+    const std::vector<std::pair<int, int>> rows = stage_hyps(S, bjobs, "beam search", w.cap_jobs);
+    for (auto& kb : rows)  // this step writes the token's K/V row into the beam's slot
+        S.hyps[kb.first].held[kb.second].push_back(S.hyps[kb.first].h[kb.second].tokens.back().id);
     const int n = (int)rows.size();
-    struct Scope {  // the state's beam switches hold for this step only (also when an error unwinds)
-        whisper_state* s;
-        ~Scope() { s->beam_k = 0; s->split_slots = false; }
-    } scope{s};
-    s->beam_k = K;
-    s->split_slots = K > 1;
-    decoder_upload(c, s, n, n, false);
-    if (s->split_slots) WM_CHECK(hipMemcpyAsync(w.sslot, w.h_sslot, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, s->stream));
-    std::vector<std::vector<float>> probs_rows;
-    const double t_step = now_ms();
-    whisper_state::DecGraph* G = dec_graph(c, s, dec_path_prepare(c, s, n), 0);
-    if (!G->pdec) {
-        WM_CHECK(hipGraphLaunch(G->exec, s->stream));
-        logits_finish(S, n, false, probs_rows);
-        kt_flush_graph(s, *G);
-    } else {  // (beam_k = 1 only) as decode_step runs a persistent step
-        bool gave_up;
-        {
-            PdecRunLock lk(c->device);
-            WM_CHECK(hipGraphLaunch(G->exec, s->stream));
-            logits_finish(S, n, false, probs_rows);
-            gave_up = *s->ws.h_pd_err != 0;
-        }
-        kt_flush_graph(s, *G);
-        if (gave_up) rerun_given_up(S, n, false, probs_rows, t_step);
+    {
+        ModeScope mode(S.s, StepMode{K, K > 1, false});
+        std::vector<std::vector<float>> probs_rows;
+        step_upload(S, n);
+        run_step(S, n, false, probs_rows);  // (K = 1 may run the persistent step, as a greedy step does)
     }
     std::vector<KvCopy> copies;
     for (int r0 = 0; r0 < n;) {
@@ -2759,15 +2741,12 @@ static void sample_start(Sched& S, const std::vector<std::pair<int, int>>& rows)
     std::vector<KvCopy> copies;
     for (int q = 0; q < (int)rows.size(); q++) {
         Job& j = S.jobs[rows[q].first];
-        BeamJob& B = S.sj[rows[q].first];
-        B.beams.assign(N, Beam());
+        std::vector<Hyp>& h = S.hyps[rows[q].first].h;
+        h.assign(N, Hyp());
         for (int b = 0; b < N; b++) {
-            Beam& bm = B.beams[b];
+            Hyp& bm = h[b];
             bm.sslot = b * n_jobs + j.slot;
-            swap_dec(j, bm);  // (the Job holds a fresh attempt's state: start_attempt)
-            const bool more = process_step(S, j, w.h_cand[q * N + b], nullptr, true);
-            swap_dec(j, bm);
-            bm.ended = !more;
+            bm.ended = !process_step(S, j, bm, w.h_cand[q * N + b], nullptr, true);
             if (b > 0 && bm.live()) copies.push_back(KvCopy{bm.sslot, j.slot, 0, (int)j.prompt.size(), 0, 0, 0});
         }
         j.phase = PH_SAMPLE;
@@ -2777,95 +2756,45 @@ static void sample_start(Sched& S, const std::vector<std::pair<int, int>>& rows)
 
 // One decode step of every live candidate of the `sjobs` clips (all in PH_SAMPLE)
 static void sample_step(Sched& S, const std::vector<int>& sjobs) {
-    Context* c = S.c;
-    whisper_state* s = S.s;
-    Workspace& w = s->ws;
-    int* hi = w.h_ints;
-    std::vector<std::pair<int, int>> rows;  // {job, candidate}
-    for (int k : sjobs) {
-        Job& j = S.jobs[k];
-        BeamJob& B = S.sj[k];
-        for (int b = 0; b < (int)B.beams.size(); b++) {
-            Beam& bm = B.beams[b];
-            if (!bm.live()) continue;
-            const int r = (int)rows.size();
-            if (r >= w.cap_jobs || r >= kSampleMaxRows) WM_FAIL("best_of: more than %d rows in a step", std::min(w.cap_jobs, kSampleMaxRows));
-            hi[r] = bm.tokens.back().id;
-            hi[w.cap_tok + r] = (int)j.prompt.size() + bm.step;
-            hi[2 * w.cap_tok + r] = j.slot;
-            hi[5 * w.cap_tok + r] = r;
-            w.h_sslot[r] = bm.sslot;
-            int* ctr = w.h_sctr + (size_t)r * 4;
-            ctr[0] = j.seek; ctr[1] = 16 * j.temp_idx + b; ctr[2] = bm.step + 1; ctr[3] = r;
-            swap_dec(j, bm);
-            fill_ctl(S, j, w.h_ctl[r], false);
-            swap_dec(j, bm);
-            rows.push_back({k, b});
-        }
-    }
+    Workspace& w = S.s->ws;
+    const std::vector<std::pair<int, int>> rows = stage_hyps(S, sjobs, "best_of", std::min(w.cap_jobs, kSampleMaxRows));
     const int n = (int)rows.size();
-    struct Scope {  // the state's switches hold for this step only (also when an error unwinds)
-        whisper_state* s;
-        bool direct;
-        ~Scope() { s->split_slots = false; s->sample_rows = false; s->direct = direct; }
-    } scope{s, s->direct};
-    s->split_slots = true;
-    s->sample_rows = true;
-    s->direct = false;
-    decoder_upload(c, s, n, n, false);
-    WM_CHECK(hipMemcpyAsync(w.sslot, w.h_sslot, n * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, s->stream));
-    WM_CHECK(hipMemcpyAsync(w.sctr, w.h_sctr, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    whisper_state::DecGraph* G = dec_graph(c, s, dec_path_prepare(c, s, n), 0);
-    if (G->pdec) WM_FAIL("best_of: a sampled step planned the persistent path");
-    WM_CHECK(hipGraphLaunch(G->exec, s->stream));
-    WM_CHECK(hipMemcpyAsync(w.h_tout, w.tout, n * sizeof(TokOut), hipMemcpyDeviceToHost, s->stream));  // the records only
-    WM_CHECK(hipStreamSynchronize(s->stream));
-    kt_flush_graph(s, *G);
+    for (int r = 0; r < n; r++) {  // the rows' draw counters
+        const Job& j = S.jobs[rows[r].first];
+        int* ctr = w.h_sctr + (size_t)r * 4;
+        ctr[0] = j.seek; ctr[1] = 16 * j.temp_idx + rows[r].second; ctr[2] = S.hyps[rows[r].first].h[rows[r].second].step + 1; ctr[3] = r;
+    }
+    {
+        ModeScope mode(S.s, StepMode{0, true, true});
+        // (rerun_given_up would not draw; split slots never plan the persistent step: pdec_use)
+        if (pdec_use(S.c, S.s, n, S.s->direct)) WM_FAIL("best_of: a sampled step planned the persistent path");
+        std::vector<std::vector<float>> probs_rows;
+        step_upload(S, n);
+        run_step(S, n, false, probs_rows);  // the records only: the rows' probs stay on the device (want_probs = 2)
+    }
     for (int r = 0; r < n; r++) {
-        Job& j = S.jobs[rows[r].first];
-        Beam& bm = S.sj[rows[r].first].beams[rows[r].second];
-        bm.step++;
-        swap_dec(j, bm);
-        const bool more = process_step(S, j, w.h_tout[r], nullptr, true);
-        swap_dec(j, bm);
-        bm.ended = !more;
+        Hyp& q = S.hyps[rows[r].first].h[rows[r].second];
+        q.ended = !process_step(S, S.jobs[rows[r].first], q, w.h_tout[r], nullptr, true);
     }
 }
 
-// Score the candidates, pick the winner (beam_winner), hand it to the Job and to attempt_done
-static void sample_finish(Sched& S, int k) {
-    Job& j = S.jobs[k];
-    BeamJob& B = S.sj[k];
-    const int N = (int)B.beams.size();
-    std::vector<double> score(N);
-    std::vector<char> failed(N);
-    std::vector<whisper_state::BeamRec> recs(N);
-    for (int b = 0; b < N; b++) {
-        Beam& bm = B.beams[b];
-        for (const TokenData& t : bm.tokens) recs[b].tokens.push_back(t.id);
-        recs[b].sum_logprobs_all = bm.sum_logprobs_all;
-        if (!bm.failed) {  // as attempt_done scores a single decoder's attempt
-            swap_dec(j, bm);
-            j.tokens.resize(j.result_len);
-            score_seq(S.p, j);
-            if (j.result_len > 32 && j.entropy < S.p.entropy_thold) j.failed = true;
-            swap_dec(j, bm);
-        }
-        score[b] = bm.score;
-        failed[b] = bm.failed;
-        recs[b].flags = (bm.completed ? 1 : 0) | (bm.failed ? 2 : 0);
+// The scheduler's pass over the clips in phase `ph` (PH_BEAM, PH_SAMPLE): a clip without a live hypothesis ends its
+// attempt (also right after the prefill; its hypotheses go to info[clip]), the live hypotheses of all the others take
+// one step together. False: the caller's abort callback fired before the step.
+static bool hyps_pass(Sched& S, Phase ph, void (*step)(Sched&, const std::vector<int>&),
+                      std::vector<std::vector<whisper_state::BeamRec>>& info) {
+    std::vector<int> jobs;
+    for (int k = 0; k < (int)S.jobs.size(); k++) {
+        if (S.jobs[k].phase != ph) continue;
+        if (S.hyps[k].live()) jobs.push_back(k);
+        else hyps_finish(S, k, S.hyps[k].h, info[k]);
     }
-    const int win = beam_winner(score, failed);
-    if (win >= 0) {
-        recs[win].flags |= 4;
-        swap_dec(j, B.beams[win]);
-    } else {
-        j.failed = true;
-    }
-    S.s->cand_info[k] = std::move(recs);
-    B.beams.clear();
-    attempt_done(S, j);
+    if (jobs.empty()) return true;
+    if (S.p.abort_callback && S.p.abort_callback(S.p.abort_callback_user_data)) return false;
+    const double td = now_ms();
+    step(S, jobs);
+    S.t_decode += now_ms() - td;
+    return true;
 }
 
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
@@ -2998,14 +2927,11 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     Sched S;
     S.c = c; S.s = s; S.p = p; S.o = o; S.single_api = single_api;
     S.beam_k = beam_k;
-    S.bj.resize(beam_k > 0 ? n_jobs : 0);
     S.sample_n = sample_n;
-    S.sj.resize(sample_n > 1 ? n_jobs : 0);
+    S.hyps.resize(beam_k > 0 || sample_n > 1 ? n_jobs : 0);
     s->beam_info.assign(n_jobs, {});
     s->cand_info.assign(n_jobs, {});
-    s->beam_k = 0;
-    s->split_slots = false;
-    s->sample_rows = false;
+    s->mode = StepMode{};
     const Vocab& v = c->vocab;
     const Hparams& hp = c->hp;
     s->results.assign(n_jobs, {});
@@ -3149,10 +3075,9 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 const double tp = now_ms();
                 const int na = (int)act.size();
                 const int det_ctx = enc_ctx(c, s);
-                int* hi = w.h_ints;
                 for (int r = 0; r < na; r++) {
-                    hi[r] = v.token_sot; hi[w.cap_tok + r] = 0; hi[2 * w.cap_tok + r] = S.jobs[act[r]].slot;
-                    hi[5 * w.cap_tok + r] = r;
+                    stage_token(w, r, v.token_sot, 0, S.jobs[act[r]].slot);
+                    w.h_ints[5 * w.cap_tok + r] = r;
                 }
                 decoder_forward(c, s, na, na);
                 std::vector<float> lg((size_t)na * 100);
@@ -3192,27 +3117,22 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
             if (!act.empty()) {
                 if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
                 const double tp = now_ms();
-                int* hi = w.h_ints;
                 int nt = 0;
                 for (int r = 0; r < (int)act.size(); r++) {
                     Job& j = S.jobs[act[r]];
                     start_attempt(S, j);
-                    for (int t = 0; t < (int)j.prompt.size(); t++) {
-                        hi[nt] = j.prompt[t]; hi[w.cap_tok + nt] = t; hi[2 * w.cap_tok + nt] = j.slot;
-                        nt++;
-                    }
-                    hi[5 * w.cap_tok + r] = nt - 1;
+                    for (int t = 0; t < (int)j.prompt.size(); t++) stage_token(w, nt++, j.prompt[t], t, j.slot);
+                    w.h_ints[5 * w.cap_tok + r] = nt - 1;
                 }
                 decoder_forward(c, s, nt, (int)act.size());
-                run_logits(S, act, true, probs_rows);
+                prefill_logits(S, act, probs_rows);
                 bool any_beam = false;
                 for (int k : act) any_beam |= beam_attempt(S, S.jobs[k]);
                 if (any_beam) {  // the same rows again through the top-k form (candidate 0 = the record above)
-                    s->beam_k = S.beam_k;
+                    ModeScope mode(s, StepMode{S.beam_k, false, false});
                     logits_launch(c, s, (int)act.size());
                     std::vector<std::vector<float>> none;
                     logits_finish(S, (int)act.size(), false, none);
-                    s->beam_k = 0;
                 }
                 S.t_prefill += now_ms() - tp;
                 copy_spot_logits(S, act);
@@ -3230,7 +3150,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                         j.phase = PH_BEAM;
                         continue;
                     }
-                    if (process_step(S, j, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) j.phase = PH_DECODE;
+                    if (process_step(S, j, j.seq, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) j.phase = PH_DECODE;
                     else attempt_done(S, j);
                 }
                 if (!copies.empty()) {  // the prompt's rows from every clip's own slot to its other beams' slots
@@ -3259,52 +3179,19 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
                 if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
                 const double td = now_ms();
                 const int na = (int)act.size();
-                step_inputs(S, act);
                 decode_step(S, act, probs_rows);
                 S.t_decode += now_ms() - td;
-                for (int r = 0; r < na; r++) S.jobs[act[r]].step++;
                 copy_spot_logits(S, act);
                 for (int r = 0; r < na; r++) {
                     Job& j = S.jobs[act[r]];
-                    if (!process_step(S, j, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) attempt_done(S, j);
+                    if (!process_step(S, j, j.seq, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) attempt_done(S, j);
                 }
             }
         }
-        // ---- beam search: one step for the live beams of every clip in a beam attempt; a clip without live
-        // beams ends its attempt (also right after the prefill)
-        {
-            std::vector<int> bjobs;
-            for (int k = 0; k < n_jobs; k++) {
-                if (S.jobs[k].phase != PH_BEAM) continue;
-                bool live = false;
-                for (const Beam& b : S.bj[k].beams) live |= b.live();
-                if (live) bjobs.push_back(k);
-                else beam_finish(S, k);
-            }
-            if (!bjobs.empty()) {
-                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
-                const double td = now_ms();
-                beam_step(S, bjobs);
-                S.t_decode += now_ms() - td;
-            }
-        }
-        // ---- sampled attempts with best_of candidates: one step for the live candidates of every such clip; a clip
-        // without live candidates ends its attempt (also right after the prefill)
-        {
-            std::vector<int> sjobs;
-            for (int k = 0; k < n_jobs; k++) {
-                if (S.jobs[k].phase != PH_SAMPLE) continue;
-                bool live = false;
-                for (const Beam& b : S.sj[k].beams) live |= b.live();
-                if (live) sjobs.push_back(k);
-                else sample_finish(S, k);
-            }
-            if (!sjobs.empty()) {
-                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
-                const double td = now_ms();
-                sample_step(S, sjobs);
-                S.t_decode += now_ms() - td;
-            }
+        // ---- beam search, then sampled attempts with best_of candidates: one step for the live hypotheses
+        if (!hyps_pass(S, PH_BEAM, beam_step, s->beam_info) || !hyps_pass(S, PH_SAMPLE, sample_step, s->cand_info)) {
+            aborted = true;
+            break;
         }
         // ---- token timestamps: align every window that just finished with new segments
         if (c->dtw) align_windows(S);

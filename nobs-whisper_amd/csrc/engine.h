@@ -190,7 +190,7 @@ struct Workspace {
     char* ring = nullptr;
     char* h_ring = nullptr;
     hipEvent_t ring_ev[2] = {nullptr, nullptr};
-    // beam search (engine.cpp beam_step): the self slot of every row of a step (rows of one clip share its cross
+    // beam search and best_of candidates (engine.cpp beam_step, sample_step): the self slot of every row of a step (rows of one clip share its cross
     // slot in `slot`), the top-k candidates [cap_jobs][kTopkMax] of the logits rows, the self-cache copies of a
     // re-parenting and the gather's staging buffer (grown on demand, 16-byte units)
     int *sslot = nullptr, *h_sslot = nullptr;
@@ -240,6 +240,17 @@ struct Job;
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
               K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
+
+// What a decode step does besides greedy's plain step (whisper_state::mode; all off between steps). topk > 0: the
+// logits launch is the top-k form with that many candidates per row (results in ws.h_cand; beam search).
+// split_slots: the rows' self slots (ws.sslot) differ from their cross slots, so the step runs the launch chain in the
+// cache form (the persistent step has one slot array). sample: the step's graph ends with launch_sample over ws.sctr
+// (best_of candidates). key(): the mode as DecGraph::beam.
+struct StepMode {
+    int topk = 0;
+    bool split_slots = false, sample = false;
+    int key() const { return topk | (split_slots ? 1 << 8 : 0) | (sample ? 1 << 9 : 0); }
+};
 
 }  // namespace wm
 
@@ -293,9 +304,8 @@ struct whisper_state {
     // pdec: 0 = launch chain, 1 = the persistent step (kernels/pdec.hip)
     // (par: 0 for the per-step path; the pipelined path alternates two instances, 0 and 1, so that one step's
     // graph events are read while the other instance runs)
-    // (beam: 0 for greedy steps; a beam-search step's graph ends with the top-k kernel for beam_k candidates and,
-    // with split_slots, reads the rows' self slots from ws.sslot: beam_k | split_slots << 8; a sampled step of best_of
-    // candidates ends with the draw kernel over the rows' probs: | 1 << 9, and `seed` = the draw's key)
+    // (beam: the step's mode, StepMode::key(): 0 for greedy steps; a sampled step's graph also depends on `seed`, the
+    // draw's key)
     // (actx: the encoder positions of the call, wm::enc_ctx: the cross-attention split counts, grid sizes and the
     // direct form's slot stride of a captured step depend on it)
     struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; };
@@ -310,18 +320,14 @@ struct whisper_state {
     double pdec_lost_ms = 0;    // wall time of the given-up launches (wait until give-up + the re-run)
     double pdec_off_until = 0;  // now_ms() clock
     bool pdec_off = false;      // the backoff as frozen once per step (dec_path_prepare), so its plan, graph and step_variant agree
-    // beam search. beam_k > 0 while a beam step runs: its logits launch is the top-k form with beam_k candidates
-    // per row (results in ws.h_cand); split_slots: its rows' self slots differ from their cross slots (beam_k > 1:
-    // launch chain only, the persistent step has one slot array). beam_info[job] = the beams of the job's last
-    // beam-searched window (whisper_mi355x_beam_info).
-    int beam_k = 0;
-    bool split_slots = false;
+    // the mode of the step that is running (a beam step, a sampled step, the prefill's top-k pass); set by
+    // engine.cpp's ModeScope for that step only
+    wm::StepMode mode;
+    // beam_info[job] = the beams of the job's last beam-searched window (whisper_mi355x_beam_info)
     struct BeamRec { std::vector<int> tokens; double sum_logprobs_all = 0; int flags = 0; };
     std::vector<std::vector<BeamRec>> beam_info;
-    // sampled attempts with best_of > 1 candidates. sample_rows: true while such a step runs (its
-    // graph ends with launch_sample over ws.sctr); sample_seed: the draws' Philox key; cand_info[job] = the
-    // candidates of the job's last such attempt (whisper_mi355x_cand_info).
-    bool sample_rows = false;
+    // sampled attempts with best_of > 1 candidates. sample_seed: the draws' Philox key; cand_info[job]
+    // = the candidates of the job's last such attempt (whisper_mi355x_cand_info).
     uint64_t sample_seed = 0;
     std::vector<std::vector<BeamRec>> cand_info;
     // cache rows the gather moved since the state was created, and what whole-sequence copies would have moved

@@ -298,3 +298,52 @@ def test_dtw_on_the_winner(wrs):
     st.close()
     plain = _run5(wrs, get_ctx(wrs, "F16"), 5)
     assert [c["tokens"] for c in cands] == [c["tokens"] for c in plain[0]]
+
+
+def _mixed_params(wrs, logprob_thold):
+    p = fallback(wrs.beam_full_params(2, "en"), 2)
+    p.logprob_thold = logprob_thold
+    return p
+
+
+def _mixed_out(st, job, single):
+    segs = st.segments() if single else st.batch_segments(job)
+    return dict(segments=segs_of(segs), decisions=st.decisions(job), beam_info=st.beam_info(job), cand_info=st.cand_info(job))
+
+
+def test_beam_and_sampled_steps_in_one_pass(wrs):
+    """Beam steps and sampled steps of different clips in the same scheduler passes, over the same host staging rows.
+    Three 40 s clips (two windows each) in one batch, BeamSearch{beam_size: 2} with best_of = 2 and temperature_inc = 0.6.
+    A first run without fallback (logprob_thold = -1e9) gives every clip's avg_logprob0 of window 0; logprob_thold is then
+    the midpoint of the widest gap between two of them, so at least one clip falls back at window 0 (its two sampled
+    candidates decode) while another goes on to the beam attempt of its window 1 in the same passes. Every clip's segments
+    (token ids, tid, p, plog), decisions, beam_info and cand_info in the batch must equal that clip run alone."""
+    ctx = get_ctx(wrs, "F16")
+    pcm = [synthetic_pcm(c, seconds=40.0) for c in (5, 7, 9)]
+    st = ctx.create_state()
+    assert st.full_batch(_mixed_params(wrs, -1e9), pcm) == 0
+    first = [st.decisions(j) for j in range(3)]
+    st.close()
+    assert all(len(d) == 2 and all(w["temp_idx"] == 0 for w in d) for d in first), first
+    lp = sorted(d[0]["avg_logprob0"] for d in first)
+    gap, lo = max((lp[i + 1] - lp[i], i) for i in range(2))
+    thold = 0.5 * (lp[lo] + lp[lo + 1])
+    print(f"avg_logprob0 of window 0: {lp}, logprob_thold {thold:.6f}")
+    assert lp[lo] < thold < lp[lo + 1], lp
+    st = ctx.create_state()
+    assert st.full_batch(_mixed_params(wrs, thold), pcm) == 0
+    batch = [_mixed_out(st, j, False) for j in range(3)]
+    st.close()
+    idx0 = [b["decisions"][0]["temp_idx"] for b in batch]
+    print(f"temp_idx of window 0: {idx0}, windows {[len(b['decisions']) for b in batch]}")
+    assert set(idx0) == {0, 1}, idx0   # (the precondition: a clip fell back at window 0, another did not)
+    # a clip decided at t = 0 went on to a second window: its beam steps ran beside the other clip's sampled steps
+    assert any(i == 0 and len(b["decisions"]) == 2 for i, b in zip(idx0, batch)), batch
+    for j in range(3):
+        st = ctx.create_state()
+        assert st.full(_mixed_params(wrs, thold), pcm[j]) == 0
+        single = _mixed_out(st, 0, True)
+        st.close()
+        assert single["segments"] and len(single["beam_info"]) == 2
+        assert (len(single["cand_info"]) == 2) == any(d["temp_idx"] == 1 for d in single["decisions"])
+        assert single == batch[j], j
