@@ -282,11 +282,7 @@ int whisper_lang_auto_detect_with_state(struct whisper_context* ctx, struct whis
         return 0;
     });
     if (rc != 0) return rc;
-    std::map<std::string, int> g_lang;
-    for (int i = 0; i < 100; i++) g_lang[k_lang_codes[i]] = i;
-    std::vector<std::pair<float, int>> ids;
-    for (auto& kv : g_lang) ids.emplace_back(lg[kv.second], kv.second);
-    std::sort(ids.begin(), ids.end(), [](const std::pair<float, int>& a, const std::pair<float, int>& b) { return a.first > b.first; });
+    std::vector<std::pair<float, int>> ids = rank_languages(lg.data());
     const float mx = ids[0].first;
     double sum = 0.0;
     for (auto& kv : ids) { kv.first = exp(kv.first - mx); sum += kv.first; }

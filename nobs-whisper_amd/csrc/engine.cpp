@@ -1572,11 +1572,22 @@ struct Sched {
     int n_max_steps;
     long decoded = 0;
     double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0, t_tokts = 0;
+    // from pass to pass of full_batch_one: the call detects every clip's language (pass_lang); apply_audio_ctx has run;
+    // a callback asked to stop; per row of the last prefill / decode step, a host-sampled row's probs
+    bool need_lang = false, ctx_applied = false, aborted = false;
+    std::vector<std::vector<float>> probs_rows;
 };
 
 static double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+struct ScopeTimer {  // ScopeTimer timed{S.t_x}: the wall time of the scope, added to one of Sched's t_* sums
+    double& sum;
+    const double t0 = now_ms();
+    ~ScopeTimer() { sum += now_ms() - t0; }
+};
+// the caller's abort callback, asked where whisper_full asks it (true: stop)
+static bool abort_asked(const Sched& S) { return S.p.abort_callback && S.p.abort_callback(S.p.abort_callback_user_data); }
 
 static void score_seq(const whisper_full_params& p, Seq& q) {
     if (q.result_len == 0) return;
@@ -1864,7 +1875,7 @@ static void align_windows(Sched& S) {
         items.push_back(std::move(it));
     }
     if (items.empty()) return;
-    const double t0 = now_ms();
+    ScopeTimer timed{S.t_align};
     ensure_align(c, s);
     hipStream_t st = s->stream;
     if (s->direct) {  // the clips' cross K/V from their encoder output, as prompts too long for the direct prefill
@@ -1934,7 +1945,6 @@ static void align_windows(Sched& S) {
         }
         i0 = i1;
     }
-    S.t_align += now_ms() - t0;
 }
 
 // Token times of every window that just finished with new segments (Job::tt_pending), whatever attempt decided it
@@ -1952,7 +1962,7 @@ static void token_time_windows(Sched& S) {
     for (int k = 0; k < (int)S.jobs.size(); k++)
         if (S.jobs[k].tt_pending) pend.push_back(k);
     if (pend.empty()) return;
-    const double t_start = now_ms();
+    ScopeTimer timed{S.t_tokts};
     std::vector<TtSeg> segs;
     std::vector<TtSpan> spans;
     struct Ref { int job; size_t seg; };
@@ -2020,7 +2030,6 @@ static void token_time_windows(Sched& S) {
         }
         j.n_new_segments = (int)(j.result.size() - j.tt_seg0);
     }
-    S.t_tokts += now_ms() - t_start;
 }
 
 // teacher-forcing hook (FullOpts::spot): the raw logits rows of the spot jobs among `act` (row r of
@@ -2423,7 +2432,6 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
     Context* c = S.c;
     whisper_state* s = S.s;
     Workspace& w = s->ws;
-    const whisper_full_params& p = S.p;
     const int n = (int)act.size();
     hipStream_t st = s->stream;
     const size_t slot_b = ring_slot_bytes(w);
@@ -2483,7 +2491,7 @@ static bool decode_pipelined(Sched& S, const std::vector<int>& act) {
                 ended = true;
             }
         }
-        const bool aborted = p.abort_callback && p.abort_callback(p.abort_callback_user_data);
+        const bool aborted = abort_asked(S);
         if (!ended && !aborted && more) {
             t_step = now_ms();
             continue;
@@ -2780,33 +2788,397 @@ static void sample_step(Sched& S, const std::vector<int>& sjobs) {
 
 // The scheduler's pass over the clips in phase `ph` (PH_BEAM, PH_SAMPLE): a clip without a live hypothesis ends its
 // attempt (also right after the prefill; its hypotheses go to info[clip]), the live hypotheses of all the others take
-// one step together. False: the caller's abort callback fired before the step.
-static bool hyps_pass(Sched& S, Phase ph, void (*step)(Sched&, const std::vector<int>&),
-                      std::vector<std::vector<whisper_state::BeamRec>>& info) {
+// one step together. A pass as full_batch_one's others: S.aborted when the abort callback fired before the step.
+static int hyps_pass(Sched& S, Phase ph, void (*step)(Sched&, const std::vector<int>&), std::vector<std::vector<whisper_state::BeamRec>>& info) {
     std::vector<int> jobs;
     for (int k = 0; k < (int)S.jobs.size(); k++) {
         if (S.jobs[k].phase != ph) continue;
         if (S.hyps[k].live()) jobs.push_back(k);
         else hyps_finish(S, k, S.hyps[k].h, info[k]);
     }
-    if (jobs.empty()) return true;
-    if (S.p.abort_callback && S.p.abort_callback(S.p.abort_callback_user_data)) return false;
-    const double td = now_ms();
+    if (jobs.empty()) return 0;
+    if (abort_asked(S)) { S.aborted = true; return 0; }
+    ScopeTimer timed{S.t_decode};
     step(S, jobs);
-    S.t_decode += now_ms() - td;
+    return 0;
+}
+static int pass_beam(Sched& S) { return hyps_pass(S, PH_BEAM, beam_step, S.s->beam_info); }
+static int pass_sample(Sched& S) { return hyps_pass(S, PH_SAMPLE, sample_step, S.s->cand_info); }
+
+// whisper_full_params.audio_ctx against the model's context: 0, or -5 and the stderr line
+static int check_audio_ctx(const Context* c, int audio_ctx) {
+    if (audio_ctx <= c->hp.n_audio_ctx) return 0;
+    fprintf(stderr, "whisper_mi355x: audio_ctx is larger than the maximum allowed (%d > %d)\n", audio_ctx, c->hp.n_audio_ctx);
+    return -5;
+}
+
+// The twin's half of a paired batch (n clips) appended to the caller's state: per-clip results, then the counters.
+// The halves ran concurrently: a phase lasted as long as its slower half; kernel time adds up.
+static void merge_twin(whisper_state* s, whisper_state* t, int n) {
+    for (int j = 0; j < n; j++) {
+        s->results.push_back(std::move(t->results[j]));
+        s->lang_ids.push_back(t->lang_ids[j]);
+        s->decisions.push_back(std::move(t->decisions[j]));
+        s->align_info.push_back(t->align_info[j]);  // (its cost matrix stays in the twin's workspace)
+        s->beam_info.push_back(std::move(t->beam_info[j]));
+        s->cand_info.push_back(std::move(t->cand_info[j]));
+    }
+    s->align_ms = std::max(s->align_ms, t->align_ms);
+    s->tokts_ms = std::max(s->tokts_ms, t->tokts_ms);
+    s->decoded_tokens += t->decoded_tokens;
+    s->pdec_give_ups += t->pdec_give_ups;
+    s->pdec_lost_ms += t->pdec_lost_ms;
+    t->pdec_give_ups = 0;
+    t->pdec_lost_ms = 0;
+    for (int k = 0; k < 5; k++) s->phase_ms[k] = std::max(s->phase_ms[k], t->phase_ms[k]);
+    for (int k = 0; k < K_NCLASS; k++) {
+        s->kstat[k].ms += t->kstat[k].ms;
+        s->kstat[k].work += t->kstat[k].work;
+        s->kstat[k].count += t->kstat[k].count;
+        t->kstat[k] = KStat();
+    }
+}
+
+// ---- full_batch_one: set-up, then a pass per phase of whisper.cpp's per-clip state machine, then the results ---------
+// Checks the call's arguments and fills S.beam_k and S.sample_n; 0, or the call's error code
+static int check_args(Sched& S, int n_jobs) {
+    const auto fail = [](int rc, const char* fmt, auto... a) { fprintf(stderr, fmt, a...); return rc; };  // one stderr line
+    // beam search: beam_size hypotheses per clip at t = 0 (DESIGN.md §11); patience is accepted and ignored
+    if (S.p.strategy == WHISPER_SAMPLING_BEAM_SEARCH) {
+        S.beam_k = std::max(1, S.p.beam_search.beam_size);
+        if (S.beam_k > kBeamMax) return fail(-4, "whisper_mi355x: beam_size %d > %d\n", S.beam_k, kBeamMax);
+        if (S.o.fixed_tokens > 0) {
+            fprintf(stderr, "whisper_mi355x: the fixed-work mode decodes greedily (no beam search)\n");
+            return -1;
+        }
+        if (S.beam_k > 1 && (long)n_jobs * S.beam_k > kBeamMaxRows)
+            return fail(-1, "whisper_mi355x: beam search of %d clips x %d beams exceeds %d decoder rows per step\n", n_jobs, S.beam_k,
+                        kBeamMaxRows);
+    } else if (S.p.strategy != WHISPER_SAMPLING_GREEDY) return fail(-100, "whisper_mi355x: unknown sampling strategy %d\n", (int)S.p.strategy);
+    // whisper.cpp uses best_of for sampled (t > 0) fallback attempts only, under both strategies: t = 0 is unaffected.
+    // (DESIGN.md §12; the fixed-work mode has no fallback)
+    S.sample_n = S.o.fixed_tokens > 0 ? 1 : std::max(1, S.p.greedy.best_of);
+    if (S.sample_n > kBeamMax) return fail(-4, "whisper_mi355x: best_of %d > %d\n", S.sample_n, kBeamMax);
+    if (S.sample_n > 1 && (long)n_jobs * S.sample_n > kBeamMaxRows) {
+        // every candidate is a decoder row with its own self slot; above the row limit sampled attempts run one
+        // host-sampled candidate per clip (the reference's Greedy{best_of: 1})
+        static const int warned = fail(0, "whisper_mi355x: best_of=%d x %d clips exceeds %d decoder rows per step: fallback attempts sample 1 candidate\n",
+                                       S.sample_n, n_jobs, kBeamMaxRows);  // (once per process)
+        S.sample_n = 1;
+    }
+    return 0;
+}
+
+// audio_ctx. whisper_full_with_state detects the language before it checks and stores
+// params.audio_ctx in the state, so the detection pass encodes at the state's earlier value (0 on a fresh state,
+// and for every clip of the batch API); this is that check-and-store, run once: after the detection pass, or before the
+// loop when there is none, or after the loop when nothing was encoded.
+static int apply_audio_ctx(Sched& S) {
+    if (S.ctx_applied || S.p.detect_language) return 0;
+    S.ctx_applied = true;
+    if (const int r = check_audio_ctx(S.c, S.p.audio_ctx)) return r;
+    S.s->audio_ctx = S.p.audio_ctx;
+    return 0;
+}
+
+// the tokens every attempt of the clip begins with, once its language is known; false: a language outside the table
+static bool build_prompt_init(Sched& S, Job& j) {
+    const Vocab& v = S.c->vocab;
+    j.prompt_init = {v.token_sot};
+    if (v.is_multilingual()) {
+        if (j.lang_id < 0) return false;
+        j.prompt_init.push_back(v.token_sot + 1 + j.lang_id);
+        j.prompt_init.push_back(S.p.translate ? v.token_translate : v.token_transcribe);
+    }
+    if (S.p.no_timestamps) j.prompt_init.push_back(v.token_not);
     return true;
 }
 
+// The clips of the call as jobs (after compute_mel): the carried and the initial prompt, the seek range, the rng, the
+// first phase. -3: the single API's auto-detect has no audio (whisper_full_with_state); -7: see build_prompt_init.
+static int make_jobs(Sched& S, const int* n, int n_jobs) {
+    const whisper_full_params& p = S.p;
+    S.need_lang = p.language == nullptr || strlen(p.language) == 0 || strcmp(p.language, "auto") == 0 || p.detect_language;
+    std::vector<int> init_prompt_tokens;
+    if (!p.prompt_tokens && p.initial_prompt) init_prompt_tokens = tokenize(S.c->vocab, p.initial_prompt);
+    else if (p.prompt_tokens && p.prompt_n_tokens > 0) init_prompt_tokens.assign(p.prompt_tokens, p.prompt_tokens + p.prompt_n_tokens);
+    const bool is_distil = S.c->hp.n_text_layer == 2 && S.c->hp.n_vocab != 51866;
+    S.p.no_timestamps = p.no_timestamps || is_distil;
+    S.jobs.resize(n_jobs);
+    for (int k = 0; k < n_jobs; k++) {
+        Job& j = S.jobs[k];
+        j.slot = k;
+        j.n_samples = n[k];
+        j.n_len = mel_n_len(n[k]);
+        j.n_len_org = mel_n_len_org(n[k]);
+        j.seek_start = p.offset_ms / 10;
+        j.seek_end = p.duration_ms == 0 ? j.n_len_org : j.seek_start + p.duration_ms / 10;
+        j.seek = j.seek_start;
+        j.rng = S.single_api ? &S.s->rng : &j.own_rng;
+        if (S.single_api) j.prompt_past = S.s->prompt_past;
+        if (p.no_context) j.prompt_past.clear();
+        if (!init_prompt_tokens.empty()) {
+            for (int t : init_prompt_tokens) j.prompt_past.push_back(t);
+            std::rotate(j.prompt_past.begin(), j.prompt_past.end() - init_prompt_tokens.size(), j.prompt_past.end());
+        }
+        const bool no_audio = S.need_lang && 0 >= j.n_len_org;  // whisper_full_with_state: failed auto-detect -> -3
+        if (no_audio && S.single_api) return -3;
+        if (no_audio || j.seek_end < j.seek_start + 10) { j.phase = PH_DONE; continue; }
+        j.lang_pending = S.need_lang;
+        if (!S.need_lang) j.lang_id = lang_index(p.language);
+        j.phase = PH_ENCODE;
+    }
+    for (auto& j : S.jobs)
+        if (j.phase != PH_DONE && !j.lang_pending && !build_prompt_init(S, j)) return -7;
+    return 0;
+}
+
+// The passes of the scheduler loop. Each takes the Sched, works on every clip that is in its phase and moves it on.
+// It returns 0, or the error code that the call returns at once (nothing is published), and sets S.aborted when a
+// callback asked to stop: the loop then ends, and the call returns 0 with the windows finished so far.
+// pass_encode encodes every window that is due. Per clip, in clip order: the progress callback, the "nothing left" test, the
+// encoder-begin callback (false stops the call), the abort callback; a stop ends the pass before anything is encoded.
+static int pass_encode(Sched& S) {
+    const whisper_full_params& p = S.p;
+    std::vector<int> wj, ws_, wsl;
+    for (int k = 0; k < (int)S.jobs.size(); k++) {
+        Job& j = S.jobs[k];
+        if (j.phase != PH_ENCODE) continue;
+        if (S.single_api && p.progress_callback) {
+            const int prog = (100 * (j.seek - j.seek_start)) / std::max(1, j.seek_end - j.seek_start);
+            p.progress_callback(S.c->owner, S.s, prog, p.progress_callback_user_data);
+        }
+        if (j.seek + 10 >= j.seek_end && !j.lang_pending) { j.phase = PH_DONE; continue; }
+        if ((S.single_api && p.encoder_begin_callback && !p.encoder_begin_callback(S.c->owner, S.s, p.encoder_begin_callback_user_data)) ||
+            abort_asked(S)) {
+            S.aborted = true;
+            return 0;
+        }
+        wj.push_back(k);
+        ws_.push_back(j.lang_pending ? 0 : j.seek);
+        wsl.push_back(j.slot);
+    }
+    if (wj.empty()) return 0;
+    { ScopeTimer timed{S.t_enc}; encode_windows(S.c, S.s, wj.data(), ws_.data(), wsl.data(), (int)wj.size()); }
+    for (int k : wj) {
+        Job& j = S.jobs[k];
+        if (j.lang_pending) { j.phase = PH_LANG; continue; }
+        if (j.seek > j.seek_start && j.seek + 500 >= j.seek_end) j.prompt_past.clear();
+        j.temp_idx = 0;
+        j.phase = PH_PREFILL;
+    }
+    return 0;
+}
+
+std::vector<std::pair<float, int>> rank_languages(const float* logits) {
+    std::map<std::string, int> g_lang;  // whisper.cpp iterates g_lang, a std::map: the codes in key order
+    for (int i = 0; i < 100; i++) g_lang[k_lang_codes[i]] = i;
+    std::vector<std::pair<float, int>> ids;
+    for (auto& kv : g_lang) ids.emplace_back(logits[kv.second], kv.second);
+    std::sort(ids.begin(), ids.end(), [](const std::pair<float, int>& a, const std::pair<float, int>& b) { return a.first > b.first; });
+    return ids;
+}
+
+// Language detection: [sot] at position 0 of every clip that waits for it, the best of the language logits. Every
+// clip of the call detects in this one pass (need_lang holds for all of them), so apply_audio_ctx follows it here.
+static int pass_lang(Sched& S) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const Vocab& v = c->vocab;
+    std::vector<int> act;
+    for (int k = 0; k < (int)S.jobs.size(); k++) if (S.jobs[k].phase == PH_LANG) act.push_back(k);
+    if (act.empty()) return 0;
+    const int na = (int)act.size();
+    const int det_ctx = enc_ctx(c, s);
+    std::vector<float> lg((size_t)na * 100);
+    {
+        ScopeTimer timed{S.t_prefill};
+        for (int r = 0; r < na; r++) {
+            stage_token(w, r, v.token_sot, 0, S.jobs[act[r]].slot);
+            w.h_ints[5 * w.cap_tok + r] = r;
+        }
+        decoder_forward(c, s, na, na);
+        for (int r = 0; r < na; r++)
+            WM_CHECK(hipMemcpyAsync(lg.data() + r * 100, w.logits + (size_t)r * c->hp.n_vocab + v.token_sot + 1, 100 * 4,
+                                    hipMemcpyDeviceToHost, s->stream));
+        WM_CHECK(hipStreamSynchronize(s->stream));
+    }
+    if (const int r = apply_audio_ctx(S)) return r;
+    // window 0 as the detection encoded it serves the first attempt only at the same audio context
+    const bool same_ctx = enc_ctx(c, s) == det_ctx;
+    for (int r = 0; r < na; r++) {
+        Job& j = S.jobs[act[r]];
+        j.lang_id = rank_languages(lg.data() + r * 100)[0].second;
+        j.lang_pending = false;
+        if (!build_prompt_init(S, j)) return -7;
+        if (S.p.detect_language) { j.phase = PH_DONE; continue; }
+        if (j.seek == 0 && same_ctx) {
+            j.temp_idx = 0;
+            j.phase = PH_PREFILL;
+        } else j.phase = PH_ENCODE;
+    }
+    return 0;
+}
+
+// Prefills every attempt that is due: the prompt rows, the logits of each last row (again in the top-k form when a
+// row is a beam attempt), then per row the attempt's first token, its beams or its best_of candidates.
+static int pass_prefill(Sched& S) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    std::vector<int> act;
+    for (int k = 0; k < (int)S.jobs.size(); k++) if (S.jobs[k].phase == PH_PREFILL) act.push_back(k);
+    if (act.empty()) return 0;
+    if (abort_asked(S)) { S.aborted = true; return 0; }
+    const int na = (int)act.size();
+    {
+        ScopeTimer timed{S.t_prefill};
+        int nt = 0;
+        for (int r = 0; r < na; r++) {
+            Job& j = S.jobs[act[r]];
+            start_attempt(S, j);
+            for (int t = 0; t < (int)j.prompt.size(); t++) stage_token(w, nt++, j.prompt[t], t, j.slot);
+            w.h_ints[5 * w.cap_tok + r] = nt - 1;
+        }
+        decoder_forward(c, s, nt, na);
+        prefill_logits(S, act, S.probs_rows);
+        bool any_beam = false;
+        for (int k : act) any_beam |= beam_attempt(S, S.jobs[k]);
+        if (any_beam) {  // the same rows again through the top-k form (candidate 0 = the record above)
+            ModeScope mode(s, StepMode{S.beam_k, false, false});
+            logits_launch(c, s, na);
+            std::vector<std::vector<float>> none;
+            logits_finish(S, na, false, none);
+        }
+    }
+    copy_spot_logits(S, act);
+    std::vector<KvCopy> copies;
+    std::vector<std::pair<int, int>> srows;  // sampled attempts with best_of candidates: {job, row}
+    for (int r = 0; r < na; r++) {
+        Job& j = S.jobs[act[r]];
+        j.no_speech_prob = w.h_tout[r].nosp_prob;
+        if (sample_attempt(S, j)) { srows.push_back({act[r], r}); continue; }
+        if (beam_attempt(S, j)) {
+            beam_start(S, act[r], w.h_cand + (size_t)r * kTopkMax, copies);
+            j.phase = PH_BEAM;
+            continue;
+        }
+        if (process_step(S, j, j.seq, w.h_tout[r], S.probs_rows[r].empty() ? nullptr : S.probs_rows[r].data())) j.phase = PH_DECODE;
+        else attempt_done(S, j);
+    }
+    if (!copies.empty()) { ScopeTimer timed{S.t_decode}; beam_gather(S, copies); }  // the prompt's rows to the other beams' slots
+    if (!srows.empty()) { ScopeTimer timed{S.t_decode}; sample_start(S, srows); }
+    return 0;
+}
+
+// Greedy and host-sampled attempts: one decode step for every clip that is decoding, or a pipelined run of steps until
+// an attempt ends (decode_pipelined) where the host has nothing to decide per step
+static int pass_decode(Sched& S) {
+    std::vector<int> act;
+    for (int k = 0; k < (int)S.jobs.size(); k++) if (S.jobs[k].phase == PH_DECODE) act.push_back(k);
+    if (act.empty()) return 0;
+    const bool pipe = pipe_ok(S, act);
+    if (abort_asked(S)) { S.aborted = true; return 0; }
+    if (pipe) { ScopeTimer timed{S.t_decode}; S.aborted = decode_pipelined(S, act); return 0; }
+    { ScopeTimer timed{S.t_decode}; decode_step(S, act, S.probs_rows); }
+    copy_spot_logits(S, act);
+    for (int r = 0; r < (int)act.size(); r++) {
+        Job& j = S.jobs[act[r]];
+        if (!process_step(S, j, j.seq, S.s->ws.h_tout[r], S.probs_rows[r].empty() ? nullptr : S.probs_rows[r].data())) attempt_done(S, j);
+    }
+    return 0;
+}
+
+// the windows that just finished with new segments: DTW alignment, then token_timestamps' t0 / t1 / vlen and max_len wrap
+static int pass_token_times(Sched& S) {
+    if (S.c->dtw) align_windows(S);
+    if (S.p.token_timestamps) token_time_windows(S);
+    return 0;
+}
+// the single-clip API's new-segment callback for the window that just finished
+static int pass_new_segment(Sched& S) {
+    if (!S.single_api || !S.p.new_segment_callback || S.jobs[0].n_new_segments <= 0) return 0;
+    Job& j = S.jobs[0];
+    S.s->results[0] = j.result;
+    S.p.new_segment_callback(S.c->owner, S.s, j.n_new_segments, S.p.new_segment_callback_user_data);
+    j.n_new_segments = 0;
+    return 0;
+}
+
+// the call's results and timings into the state and the context
+static void publish(Sched& S) {
+    whisper_state* s = S.s;
+    for (size_t k = 0; k < S.jobs.size(); k++) {
+        s->results[k] = std::move(S.jobs[k].result);
+        s->lang_ids[k] = S.jobs[k].lang_id;
+        s->decisions[k] = std::move(S.jobs[k].decisions);
+    }
+    if (S.single_api && !S.jobs.empty()) {
+        s->prompt_past = S.jobs[0].prompt_past;
+        s->lang_id = S.jobs[0].lang_id;
+    }
+    kt_flush(s);
+    s->decoded_tokens = S.decoded;
+    g_decoded_tokens_total += S.decoded;
+    s->phase_ms[0] = S.t_mel; s->phase_ms[1] = S.t_enc; s->phase_ms[2] = S.t_prefill; s->phase_ms[3] = S.t_decode; s->phase_ms[4] = S.t_logits;
+    s->align_ms = S.t_align;
+    s->tokts_ms = S.t_tokts;
+    std::lock_guard<std::mutex> lk(S.c->timings_mu);
+    S.c->timings.encode_ms += (float)S.t_enc;
+    S.c->timings.decode_ms += (float)S.t_decode;
+    S.c->timings.prompt_ms += (float)S.t_prefill;
+}
+
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
-                          int n_jobs, bool on_device, const FullOpts& o, bool single_api);
+                          int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
+    WM_CHECK(hipSetDevice(c->device));
+    Sched S;
+    S.c = c; S.s = s; S.p = p; S.o = o; S.single_api = single_api;
+    if (const int r = check_args(S, n_jobs)) return r;
+    ensure_expanded(c, s->stream);  // quantized files: before anything is captured
+    S.hyps.resize(S.beam_k > 0 || S.sample_n > 1 ? n_jobs : 0);
+    s->beam_info.assign(n_jobs, {});
+    s->cand_info.assign(n_jobs, {});
+    s->mode = StepMode{};
+    s->results.assign(n_jobs, {});
+    s->lang_ids.assign(n_jobs, 0);
+    s->decisions.assign(n_jobs, {});
+    s->align_info.assign(n_jobs, {});
+    s->align_ms = s->tokts_ms = 0;
+    s->decoded_tokens = 0;
+    {
+        ScopeTimer timed{S.t_mel};
+        // beams of one clip share its cross K/V cache slot: beam_k > 1 runs in the cache form, with a self slot per beam
+        // (best_of candidates take self slots too, but the call keeps the cross form that it takes with best_of = 1)
+        s->direct = S.beam_k > 1 ? false : pick_direct(c, n_jobs);
+        ensure_ws(c, s, n_jobs * std::max(1, std::max(S.beam_k, S.sample_n)), n_jobs);
+        if (!single_api) s->audio_ctx = 0;  // every clip of the batch API starts as on a fresh state (apply_audio_ctx)
+        compute_mel(c, s, pcm, n, n_jobs, on_device);
+    }
+    if (p.token_timestamps) { ScopeTimer timed{S.t_tokts}; compute_energy(s, pcm, n, n_jobs, on_device); }
+    if (p.temperature_inc > 0.0f && o.fixed_tokens <= 0)
+        for (float t = p.temperature; t < 1.0f + 1e-6f; t += p.temperature_inc) S.temps.push_back(t);
+    if (S.temps.empty()) S.temps.push_back(p.temperature);
+    S.n_max_steps = o.fixed_tokens > 0 ? o.fixed_tokens : c->hp.n_text_ctx / 2 - 4;
+    if (const int r = make_jobs(S, n, n_jobs)) return r;
+    if (!S.need_lang)
+        if (const int r = apply_audio_ctx(S)) return r;
+    static int (*const kPasses[])(Sched&) = {pass_encode, pass_lang, pass_prefill, pass_decode, pass_beam, pass_sample, pass_token_times, pass_new_segment};
+    int rc = 0;
+    while (rc == 0 && !S.aborted && std::any_of(S.jobs.begin(), S.jobs.end(), [](const Job& j) { return j.phase != PH_DONE; }))
+        for (auto pass : kPasses)
+            if ((rc = pass(S)) != 0 || S.aborted) break;
+    if (rc) return rc;
+    if (const int r = apply_audio_ctx(S)) return r;  // (if no pass did: no clip had a window to encode, or a stop came first)
+    publish(S);
+    return 0;
+}
 
 int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
     if (single_api || n_jobs <= kPairMin) return full_batch_one(c, s, p, pcm, n, n_jobs, on_device, o, single_api);
-    if (p.audio_ctx > c->hp.n_audio_ctx) {  // (before the halves start: one line, not one per half)
-        fprintf(stderr, "whisper_mi355x: audio_ctx is larger than the maximum allowed (%d > %d)\n", p.audio_ctx, c->hp.n_audio_ctx);
-        return -5;
-    }
+    if (const int r = check_audio_ctx(c, p.audio_ctx)) return r;  // (before the halves start: one line, not one per half)
     WM_CHECK(hipSetDevice(c->device));
     if (!s->twin) s->twin = create_state(c);
     whisper_state* t = s->twin;
@@ -2856,380 +3228,7 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
     if (eb) std::rethrow_exception(eb);
     if (ra) return ra;
     if (rb) return rb;
-    for (int j = 0; j < n_jobs - na; j++) {
-        s->results.push_back(std::move(t->results[j]));
-        s->lang_ids.push_back(t->lang_ids[j]);
-        s->decisions.push_back(std::move(t->decisions[j]));
-        s->align_info.push_back(t->align_info[j]);  // (its cost matrix stays in the twin's workspace)
-        s->beam_info.push_back(std::move(t->beam_info[j]));
-        s->cand_info.push_back(std::move(t->cand_info[j]));
-    }
-    s->align_ms = std::max(s->align_ms, t->align_ms);
-    s->tokts_ms = std::max(s->tokts_ms, t->tokts_ms);
-    s->decoded_tokens += t->decoded_tokens;
-    s->pdec_give_ups += t->pdec_give_ups;
-    s->pdec_lost_ms += t->pdec_lost_ms;
-    t->pdec_give_ups = 0;
-    t->pdec_lost_ms = 0;
-    // the halves ran concurrently: a phase lasted as long as its slower half; kernel time adds up
-    for (int k = 0; k < 5; k++) s->phase_ms[k] = std::max(s->phase_ms[k], t->phase_ms[k]);
-    for (int k = 0; k < K_NCLASS; k++) {
-        s->kstat[k].ms += t->kstat[k].ms;
-        s->kstat[k].work += t->kstat[k].work;
-        s->kstat[k].count += t->kstat[k].count;
-        t->kstat[k] = KStat();
-    }
-    return 0;
-}
-
-static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
-                          int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
-    WM_CHECK(hipSetDevice(c->device));
-    // beam search: beam_size hypotheses per clip at t = 0 (DESIGN.md §11); patience is accepted and ignored
-    int beam_k = 0;
-    if (p.strategy == WHISPER_SAMPLING_BEAM_SEARCH) {
-        beam_k = std::max(1, p.beam_search.beam_size);
-        if (beam_k > kBeamMax) {
-            fprintf(stderr, "whisper_mi355x: beam_size %d > %d\n", beam_k, kBeamMax);
-            return -4;
-        }
-        if (o.fixed_tokens > 0) {
-            fprintf(stderr, "whisper_mi355x: the fixed-work mode decodes greedily (no beam search)\n");
-            return -1;
-        }
-        if (beam_k > 1 && (long)n_jobs * beam_k > kBeamMaxRows) {
-            fprintf(stderr, "whisper_mi355x: beam search of %d clips x %d beams exceeds %d decoder rows per step\n", n_jobs, beam_k,
-                    kBeamMaxRows);
-            return -1;
-        }
-    } else if (p.strategy != WHISPER_SAMPLING_GREEDY) {
-        fprintf(stderr, "whisper_mi355x: unknown sampling strategy %d\n", (int)p.strategy);
-        return -100;
-    }
-    // whisper.cpp uses best_of for sampled (t > 0) fallback attempts only, under both strategies: t = 0 is unaffected.
-    // (DESIGN.md §12; the fixed-work mode has no fallback)
-    int sample_n = o.fixed_tokens > 0 ? 1 : std::max(1, p.greedy.best_of);
-    if (sample_n > kBeamMax) {
-        fprintf(stderr, "whisper_mi355x: best_of %d > %d\n", sample_n, kBeamMax);
-        return -4;
-    }
-    if (sample_n > 1 && (long)n_jobs * sample_n > kBeamMaxRows) {
-        // every candidate is a decoder row with its own self slot; above the row limit sampled attempts run one
-        // host-sampled candidate per clip (the reference's Greedy{best_of: 1})
-        static bool warned = false;
-        if (!warned)
-            fprintf(stderr, "whisper_mi355x: best_of=%d x %d clips exceeds %d decoder rows per step: fallback attempts sample 1 candidate\n",
-                    sample_n, n_jobs, kBeamMaxRows);
-        warned = true;
-        sample_n = 1;
-    }
-    ensure_expanded(c, s->stream);  // quantized files: before anything is captured
-    Sched S;
-    S.c = c; S.s = s; S.p = p; S.o = o; S.single_api = single_api;
-    S.beam_k = beam_k;
-    S.sample_n = sample_n;
-    S.hyps.resize(beam_k > 0 || sample_n > 1 ? n_jobs : 0);
-    s->beam_info.assign(n_jobs, {});
-    s->cand_info.assign(n_jobs, {});
-    s->mode = StepMode{};
-    const Vocab& v = c->vocab;
-    const Hparams& hp = c->hp;
-    s->results.assign(n_jobs, {});
-    s->lang_ids.assign(n_jobs, 0);
-    s->decisions.assign(n_jobs, {});
-    s->align_info.assign(n_jobs, {});
-    s->align_ms = 0;
-    s->tokts_ms = 0;
-    s->decoded_tokens = 0;
-    double t0 = now_ms();
-    // beams of one clip share its cross K/V cache slot: beam_k > 1 runs in the cache form, with a self slot per beam
-    s->direct = beam_k > 1 ? false : pick_direct(c, n_jobs);
-    // (best_of candidates take self slots like beams, but the call keeps its own cross form: the t = 0 attempt's plan
-    // is the one it takes with best_of = 1)
-    ensure_ws(c, s, n_jobs * std::max(1, std::max(beam_k, sample_n)), n_jobs);
-    // audio_ctx. whisper_full_with_state detects the language before it checks and stores
-    // params.audio_ctx in the state, so the detection pass encodes at the state's earlier value (0 on a fresh state,
-    // and for every clip of the batch API); apply_audio_ctx is that check-and-store, run once after the detection
-    // (or before the first window when there is none).
-    if (!single_api) s->audio_ctx = 0;
-    bool ctx_applied = false;
-    auto apply_audio_ctx = [&]() -> int {
-        ctx_applied = true;
-        if (p.audio_ctx > hp.n_audio_ctx) {
-            fprintf(stderr, "whisper_mi355x: audio_ctx is larger than the maximum allowed (%d > %d)\n", p.audio_ctx, hp.n_audio_ctx);
-            return -5;
-        }
-        s->audio_ctx = p.audio_ctx;
-        return 0;
-    };
-    compute_mel(c, s, pcm, n, n_jobs, on_device);
-    S.t_mel = now_ms() - t0;
-    if (p.token_timestamps) {
-        const double te = now_ms();
-        compute_energy(s, pcm, n, n_jobs, on_device);
-        S.t_tokts += now_ms() - te;
-    }
-
-    if (p.temperature_inc > 0.0f && o.fixed_tokens <= 0)
-        for (float t = p.temperature; t < 1.0f + 1e-6f; t += p.temperature_inc) S.temps.push_back(t);
-    if (S.temps.empty()) S.temps.push_back(p.temperature);
-    const int n_max = hp.n_text_ctx / 2 - 4;
-    S.n_max_steps = o.fixed_tokens > 0 ? o.fixed_tokens : n_max;
-    const bool need_lang = p.language == nullptr || strlen(p.language) == 0 || strcmp(p.language, "auto") == 0 || p.detect_language;
-    std::vector<int> init_prompt_tokens;
-    if (!p.prompt_tokens && p.initial_prompt) init_prompt_tokens = tokenize(v, p.initial_prompt);
-    else if (p.prompt_tokens && p.prompt_n_tokens > 0) init_prompt_tokens.assign(p.prompt_tokens, p.prompt_tokens + p.prompt_n_tokens);
-    const bool is_distil = hp.n_text_layer == 2 && hp.n_vocab != 51866;
-    const bool no_ts = p.no_timestamps || is_distil;
-    S.p.no_timestamps = no_ts;
-
-    S.jobs.resize(n_jobs);
-    for (int k = 0; k < n_jobs; k++) {
-        Job& j = S.jobs[k];
-        j.slot = k;
-        j.n_samples = n[k];
-        j.n_len = mel_n_len(n[k]);
-        j.n_len_org = mel_n_len_org(n[k]);
-        j.seek_start = p.offset_ms / 10;
-        j.seek_end = p.duration_ms == 0 ? j.n_len_org : j.seek_start + p.duration_ms / 10;
-        j.seek = j.seek_start;
-        j.rng = single_api ? &s->rng : &j.own_rng;
-        if (single_api) j.prompt_past = s->prompt_past;
-        if (p.no_context) j.prompt_past.clear();
-        if (!init_prompt_tokens.empty()) {
-            for (int t : init_prompt_tokens) j.prompt_past.push_back(t);
-            std::rotate(j.prompt_past.begin(), j.prompt_past.end() - init_prompt_tokens.size(), j.prompt_past.end());
-        }
-        if (need_lang && 0 >= j.n_len_org) {  // whisper_full_with_state: failed auto-detect -> -3
-            if (single_api) return -3;
-            j.phase = PH_DONE;
-            continue;
-        }
-        if (j.seek_end < j.seek_start + 10) { j.phase = PH_DONE; continue; }
-        j.lang_pending = need_lang;
-        if (!need_lang) j.lang_id = lang_index(p.language);
-        j.phase = PH_ENCODE;
-    }
-    auto build_prompt_init = [&](Job& j) -> bool {
-        j.prompt_init = {v.token_sot};
-        if (v.is_multilingual()) {
-            if (j.lang_id < 0) return false;
-            j.prompt_init.push_back(v.token_sot + 1 + j.lang_id);
-            j.prompt_init.push_back(p.translate ? v.token_translate : v.token_transcribe);
-        }
-        if (no_ts) j.prompt_init.push_back(v.token_not);
-        return true;
-    };
-    for (auto& j : S.jobs)
-        if (j.phase != PH_DONE && !j.lang_pending && !build_prompt_init(j)) return -7;
-    if (!need_lang)
-        if (const int r = apply_audio_ctx()) return r;
-
-    Workspace& w = s->ws;
-    std::vector<std::vector<float>> probs_rows;
-    bool aborted = false;
-    while (!aborted) {
-        bool any = false;
-        for (auto& j : S.jobs) any |= j.phase != PH_DONE;
-        if (!any) break;
-        // ---- encode every window that is due
-        {
-            std::vector<int> wj, ws_, wsl;
-            for (int k = 0; k < n_jobs; k++) {
-                Job& j = S.jobs[k];
-                if (j.phase != PH_ENCODE) continue;
-                if (single_api && p.progress_callback) {
-                    const int prog = (100 * (j.seek - j.seek_start)) / std::max(1, j.seek_end - j.seek_start);
-                    p.progress_callback(c->owner, s, prog, p.progress_callback_user_data);
-                }
-                if (j.seek + 10 >= j.seek_end && !j.lang_pending) { j.phase = PH_DONE; continue; }
-                if (single_api && p.encoder_begin_callback &&
-                    !p.encoder_begin_callback(c->owner, s, p.encoder_begin_callback_user_data)) {
-                    aborted = true;
-                    break;
-                }
-                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
-                wj.push_back(k);
-                ws_.push_back(j.lang_pending ? 0 : j.seek);
-                wsl.push_back(j.slot);
-            }
-            if (aborted) break;
-            if (!wj.empty()) {
-                const double te = now_ms();
-                encode_windows(c, s, wj.data(), ws_.data(), wsl.data(), (int)wj.size());
-                S.t_enc += now_ms() - te;
-                for (int k : wj) {
-                    Job& j = S.jobs[k];
-                    if (j.lang_pending) { j.phase = PH_LANG; continue; }
-                    if (j.seek > j.seek_start && j.seek + 500 >= j.seek_end) j.prompt_past.clear();
-                    j.temp_idx = 0;
-                    j.phase = PH_PREFILL;
-                }
-            }
-        }
-        // ---- language detection: decode [sot] at pos 0, argmax over the language logits
-        {
-            std::vector<int> act;
-            for (int k = 0; k < n_jobs; k++) if (S.jobs[k].phase == PH_LANG) act.push_back(k);
-            if (!act.empty()) {
-                const double tp = now_ms();
-                const int na = (int)act.size();
-                const int det_ctx = enc_ctx(c, s);
-                for (int r = 0; r < na; r++) {
-                    stage_token(w, r, v.token_sot, 0, S.jobs[act[r]].slot);
-                    w.h_ints[5 * w.cap_tok + r] = r;
-                }
-                decoder_forward(c, s, na, na);
-                std::vector<float> lg((size_t)na * 100);
-                for (int r = 0; r < na; r++)
-                    WM_CHECK(hipMemcpyAsync(lg.data() + r * 100, w.logits + (size_t)r * hp.n_vocab + v.token_sot + 1, 100 * 4,
-                                            hipMemcpyDeviceToHost, s->stream));
-                WM_CHECK(hipStreamSynchronize(s->stream));
-                S.t_prefill += now_ms() - tp;
-                // (every clip of the call detects in this one pass: need_lang holds for all of them)
-                if (!ctx_applied && !p.detect_language)
-                    if (const int r = apply_audio_ctx()) return r;
-                // window 0 as the detection encoded it serves the first attempt only at the same audio context
-                const bool same_ctx = enc_ctx(c, s) == det_ctx;
-                for (int r = 0; r < na; r++) {
-                    Job& j = S.jobs[act[r]];
-                    // whisper_lang_auto_detect_with_state: iterate g_lang (std::map, key order), sort desc
-                    std::map<std::string, int> g_lang;
-                    for (int i = 0; i < 100; i++) g_lang[k_lang_codes[i]] = i;
-                    std::vector<std::pair<float, int>> ids;
-                    for (auto& kv : g_lang) ids.emplace_back(lg[r * 100 + kv.second], kv.second);
-                    std::sort(ids.begin(), ids.end(), [](const std::pair<float, int>& a, const std::pair<float, int>& b) { return a.first > b.first; });
-                    j.lang_id = ids[0].second;
-                    j.lang_pending = false;
-                    if (!build_prompt_init(j)) return -7;
-                    if (p.detect_language) { j.phase = PH_DONE; continue; }
-                    if (j.seek == 0 && same_ctx) {
-                        j.temp_idx = 0;
-                        j.phase = PH_PREFILL;
-                    } else j.phase = PH_ENCODE;
-                }
-            }
-        }
-        // ---- prefill every attempt that is due
-        {
-            std::vector<int> act;
-            for (int k = 0; k < n_jobs; k++) if (S.jobs[k].phase == PH_PREFILL) act.push_back(k);
-            if (!act.empty()) {
-                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
-                const double tp = now_ms();
-                int nt = 0;
-                for (int r = 0; r < (int)act.size(); r++) {
-                    Job& j = S.jobs[act[r]];
-                    start_attempt(S, j);
-                    for (int t = 0; t < (int)j.prompt.size(); t++) stage_token(w, nt++, j.prompt[t], t, j.slot);
-                    w.h_ints[5 * w.cap_tok + r] = nt - 1;
-                }
-                decoder_forward(c, s, nt, (int)act.size());
-                prefill_logits(S, act, probs_rows);
-                bool any_beam = false;
-                for (int k : act) any_beam |= beam_attempt(S, S.jobs[k]);
-                if (any_beam) {  // the same rows again through the top-k form (candidate 0 = the record above)
-                    ModeScope mode(s, StepMode{S.beam_k, false, false});
-                    logits_launch(c, s, (int)act.size());
-                    std::vector<std::vector<float>> none;
-                    logits_finish(S, (int)act.size(), false, none);
-                }
-                S.t_prefill += now_ms() - tp;
-                copy_spot_logits(S, act);
-                std::vector<KvCopy> copies;
-                std::vector<std::pair<int, int>> srows;  // sampled attempts with best_of candidates: {job, row}
-                for (int r = 0; r < (int)act.size(); r++) {
-                    Job& j = S.jobs[act[r]];
-                    j.no_speech_prob = w.h_tout[r].nosp_prob;
-                    if (sample_attempt(S, j)) {
-                        srows.push_back({act[r], r});
-                        continue;
-                    }
-                    if (beam_attempt(S, j)) {
-                        beam_start(S, act[r], w.h_cand + (size_t)r * kTopkMax, copies);
-                        j.phase = PH_BEAM;
-                        continue;
-                    }
-                    if (process_step(S, j, j.seq, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) j.phase = PH_DECODE;
-                    else attempt_done(S, j);
-                }
-                if (!copies.empty()) {  // the prompt's rows from every clip's own slot to its other beams' slots
-                    const double tg = now_ms();
-                    beam_gather(S, copies);
-                    S.t_decode += now_ms() - tg;
-                }
-                if (!srows.empty()) {
-                    const double tg = now_ms();
-                    sample_start(S, srows);
-                    S.t_decode += now_ms() - tg;
-                }
-            }
-        }
-        // ---- one decode step for every clip that is decoding
-        {
-            std::vector<int> act;
-            for (int k = 0; k < n_jobs; k++) if (S.jobs[k].phase == PH_DECODE) act.push_back(k);
-            if (!act.empty() && pipe_ok(S, act)) {
-                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
-                const double td = now_ms();
-                const bool ab = decode_pipelined(S, act);
-                S.t_decode += now_ms() - td;
-                if (ab) { aborted = true; break; }
-            } else if (!act.empty()) {
-                if (p.abort_callback && p.abort_callback(p.abort_callback_user_data)) { aborted = true; break; }
-                const double td = now_ms();
-                const int na = (int)act.size();
-                decode_step(S, act, probs_rows);
-                S.t_decode += now_ms() - td;
-                copy_spot_logits(S, act);
-                for (int r = 0; r < na; r++) {
-                    Job& j = S.jobs[act[r]];
-                    if (!process_step(S, j, j.seq, w.h_tout[r], probs_rows[r].empty() ? nullptr : probs_rows[r].data())) attempt_done(S, j);
-                }
-            }
-        }
-        // ---- beam search, then sampled attempts with best_of candidates: one step for the live hypotheses
-        if (!hyps_pass(S, PH_BEAM, beam_step, s->beam_info) || !hyps_pass(S, PH_SAMPLE, sample_step, s->cand_info)) {
-            aborted = true;
-            break;
-        }
-        // ---- token timestamps: align every window that just finished with new segments
-        if (c->dtw) align_windows(S);
-        // ---- token_timestamps: t0 / t1 / vlen of the new segments' tokens, then the max_len wrap
-        if (p.token_timestamps) token_time_windows(S);
-        // ---- new-segment callback (whisper.h single-clip API)
-        if (single_api && p.new_segment_callback) {
-            Job& j = S.jobs[0];
-            if (j.n_new_segments > 0) {
-                s->results[0] = j.result;
-                p.new_segment_callback(c->owner, s, j.n_new_segments,
-                                       p.new_segment_callback_user_data);
-                j.n_new_segments = 0;
-            }
-        }
-    }
-    if (!ctx_applied && !p.detect_language)  // (no clip had a window to encode)
-        if (const int r = apply_audio_ctx()) return r;
-    for (int k = 0; k < n_jobs; k++) {
-        s->results[k] = std::move(S.jobs[k].result);
-        s->lang_ids[k] = S.jobs[k].lang_id;
-        s->decisions[k] = std::move(S.jobs[k].decisions);
-    }
-    if (single_api && n_jobs > 0) {
-        s->prompt_past = S.jobs[0].prompt_past;
-        s->lang_id = S.jobs[0].lang_id;
-    }
-    kt_flush(s);
-    s->decoded_tokens = S.decoded;
-    g_decoded_tokens_total += S.decoded;
-    s->phase_ms[0] = S.t_mel; s->phase_ms[1] = S.t_enc; s->phase_ms[2] = S.t_prefill; s->phase_ms[3] = S.t_decode;
-    s->phase_ms[4] = S.t_logits;
-    s->align_ms = S.t_align;
-    s->tokts_ms = S.t_tokts;
-    std::lock_guard<std::mutex> lk(c->timings_mu);
-    c->timings.encode_ms += (float)S.t_enc;
-    c->timings.decode_ms += (float)S.t_decode;
-    c->timings.prompt_ms += (float)S.t_prefill;
+    merge_twin(s, t, n_jobs - na);
     return 0;
 }
 

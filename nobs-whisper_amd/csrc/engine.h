@@ -233,8 +233,6 @@ struct Workspace {
     int tt_cap_clips = 0, tt_cap_segs = 0, tt_cap_spans = 0;
 };
 
-struct Job;
-
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
@@ -378,4 +376,7 @@ int compute_mel(Context* c, whisper_state* s, const float* const* pcm, const int
 int encode_windows(Context* c, whisper_state* s, const int* jobs, const int* seeks, const int* slots, int n_win);
 int decode_tokens(Context* c, whisper_state* s, const int* tokens, const int* pos, const int* slots, int n_tok,
                   const int* logit_rows, int n_logit_rows);
+// whisper_lang_auto_detect_with_state's ranking of a row's 100 language logits: {logit, language id}, best first
+// (std::sort over the languages in code order, as whisper.cpp: equal logits resolve as there)
+std::vector<std::pair<float, int>> rank_languages(const float* logits);
 }  // namespace wm
