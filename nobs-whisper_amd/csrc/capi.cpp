@@ -31,6 +31,41 @@ template <typename F> static int guarded(whisper_state* s, F&& f) {
     return WHISPER_MI355X_ERR_RUNTIME;
 }
 
+// ---- what the kernel-level hooks below own: released also when a launcher refuses the shape (WM_FAIL throws) ----
+struct HookStream {
+    hipStream_t st = nullptr;
+    HookStream() { WM_CHECK(hipStreamCreate(&st)); }
+    ~HookStream() { hipStreamDestroy(st); }
+};
+struct HookBufs {  // device buffers
+    std::vector<void*> p;
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        WM_CHECK(hipMalloc(&q, bytes));
+        p.push_back(q);
+        return q;
+    }
+    ~HookBufs() { for (void* q : p) hipFree(q); }
+};
+struct HookEvent {
+    hipEvent_t e = nullptr;
+    HookEvent() { WM_CHECK(hipEventCreate(&e)); }
+    ~HookEvent() { hipEventDestroy(e); }
+};
+// `run` reps times on the stream between two events: the average ms per run, 0 at reps == 0; warm: one run
+// before the first event
+template <typename F> static float timed_ms(hipStream_t st, int reps, bool warm, F run) {
+    HookEvent e0, e1;
+    if (warm) run();
+    WM_CHECK(hipEventRecord(e0.e, st));
+    for (int r = 0; r < reps; r++) run();
+    WM_CHECK(hipEventRecord(e1.e, st));
+    WM_CHECK(hipStreamSynchronize(st));
+    float t = 0;
+    WM_CHECK(hipEventElapsedTime(&t, e0.e, e1.e));
+    return reps > 0 ? t / reps : 0.0f;
+}
+
 static DType env_dtype(DType def) {
     const char* e = getenv("WHISPER_MI355X_DTYPE");
     if (!e) return def;
@@ -648,41 +683,22 @@ int whisper_mi355x_debug_gemm(struct whisper_context* ctx, int epi, const void* 
         const int T = ctx->c.hp.n_audio_ctx;
         if (epi == EPI_CROSSKV && (M % T != 0 || K % 64 != 0 || N % (2 * K) != 0)) return -1;
         hipSetDevice(ctx->c.device);
-        hipStream_t st;
-        WM_CHECK(hipStreamCreate(&st));
-        GemmArgs g{};
-        g.A = A; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
-        g.B = B; g.bias = bias; g.M = M; g.N = N; g.K = K;
-        g.out = out; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
-        g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
+        HookBufs b;
+        HookStream hs;
+        GemmArgs g = gemm_plain(A, M, K, B, N, bias, out, N);
         if (M <= 128) {  // decode-step shapes take the split-K path, as in the engine
             g.splitk_ws_elems = 64L * M * N;
-            WM_CHECK(hipMalloc(&g.splitk_ws, g.splitk_ws_elems * sizeof(float)));
+            g.splitk_ws = (float*)b.get(g.splitk_ws_elems * sizeof(float));
         }
-        int* dslot = nullptr;
         if (epi == EPI_CROSSKV) {
-            std::vector<int> hs(M / T);
-            for (int i = 0; i < M / T; i++) hs[i] = i;
-            WM_CHECK(hipMalloc((void**)&dslot, hs.size() * sizeof(int)));
-            WM_CHECK(hipMemcpy(dslot, hs.data(), hs.size() * sizeof(int), hipMemcpyHostToDevice));
+            std::vector<int> slots(M / T);
+            for (int i = 0; i < M / T; i++) slots[i] = i;
+            int* dslot = (int*)b.get(slots.size() * sizeof(int));
+            WM_CHECK(hipMemcpy(dslot, slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice));
             g.cache = out; g.row_slot = dslot; g.d = K; g.H = K / 64; g.ctx = T; g.L = N / (2 * K); g.layer = 0;
         }
-        hipEvent_t e0, e1;
-        WM_CHECK(hipEventCreate(&e0));
-        WM_CHECK(hipEventCreate(&e1));
-        launch_gemm(ctx->c.dt, epi, g, st);  // warm
-        WM_CHECK(hipEventRecord(e0, st));
-        for (int r = 0; r < reps; r++) launch_gemm(ctx->c.dt, epi, g, st);
-        WM_CHECK(hipEventRecord(e1, st));
-        WM_CHECK(hipStreamSynchronize(st));
-        float t = 0;
-        WM_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = reps > 0 ? t / reps : 0.0f;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        hipStreamDestroy(st);
-        if (g.splitk_ws) hipFree(g.splitk_ws);
-        if (dslot) hipFree(dslot);
+        const float t = timed_ms(hs.st, reps, true, [&] { launch_gemm(ctx->c.dt, epi, g, hs.st); });
+        if (ms) *ms = t;
         return 0;
     });
 }
@@ -692,28 +708,11 @@ int whisper_mi355x_debug_gemm_small(struct whisper_context* ctx, int epi, const 
     return guarded(nullptr, [&]() -> int {
         if (!ctx || !gemm_small_ok(M, K, ln_w != nullptr)) return -1;
         hipSetDevice(ctx->c.device);
-        hipStream_t st;
-        WM_CHECK(hipStreamCreate(&st));
-        GemmArgs g{};
-        g.A = A; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
-        g.B = B; g.bias = bias; g.M = M; g.N = N; g.K = K;
-        g.out = out; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
-        g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
+        HookStream hs;
+        GemmArgs g = gemm_plain(A, M, K, B, N, bias, out, N);
         g.a_ln_w = ln_w; g.a_ln_b = ln_b;
-        hipEvent_t e0, e1;
-        WM_CHECK(hipEventCreate(&e0));
-        WM_CHECK(hipEventCreate(&e1));
-        launch_gemm_small(ctx->c.dt, epi, g, ln_w != nullptr, st);
-        WM_CHECK(hipEventRecord(e0, st));
-        for (int r = 0; r < reps; r++) launch_gemm_small(ctx->c.dt, epi, g, ln_w != nullptr, st);
-        WM_CHECK(hipEventRecord(e1, st));
-        WM_CHECK(hipStreamSynchronize(st));
-        float t = 0;
-        WM_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = reps > 0 ? t / reps : 0.0f;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        hipStreamDestroy(st);
+        const float t = timed_ms(hs.st, reps, true, [&] { launch_gemm_small(ctx->c.dt, epi, g, ln_w != nullptr, hs.st); });
+        if (ms) *ms = t;
         return 0;
     });
 }
@@ -766,14 +765,13 @@ int whisper_mi355x_debug_gemm_small_q(struct whisper_context* ctx, int epi, cons
             !debug_qmat(&q, type, qs, qh, dm))
             return -1;
         hipSetDevice(ctx->c.device);
-        GemmArgs g{};
-        g.A = A; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
-        g.B = nullptr; g.q = q; g.bias = bias; g.M = M; g.N = N; g.K = K;
-        g.out = out; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
+        HookStream hs;
+        GemmArgs g = gemm_plain(A, M, K, nullptr, N, bias, out, N);
+        g.q = q;
         g.sc_div = N; g.sc_mod = 1; g.sc_lim = 1; g.scale = scale;  // every column scaled (EPI_STORE), as the cross-Q call
         g.a_ln_w = ln_w; g.a_ln_b = ln_b;
-        launch_gemm_small(ctx->c.dt, epi, g, ln_w != nullptr, nullptr);
-        WM_CHECK(hipDeviceSynchronize());
+        launch_gemm_small(ctx->c.dt, epi, g, ln_w != nullptr, hs.st);
+        WM_CHECK(hipStreamSynchronize(hs.st));
         return 0;
     });
 }
@@ -783,27 +781,10 @@ int whisper_mi355x_debug_gemm_fp8(struct whisper_context* ctx, int epi, const vo
     return guarded(nullptr, [&]() -> int {
         if (!ctx) return -1;
         hipSetDevice(ctx->c.device);
-        hipStream_t st;
-        WM_CHECK(hipStreamCreate(&st));
-        GemmArgs g{};
-        g.A = A8; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
-        g.B = B8; g.bias = bias; g.M = M; g.N = N; g.K = K;
-        g.out = out; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
-        g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
-        hipEvent_t e0, e1;
-        WM_CHECK(hipEventCreate(&e0));
-        WM_CHECK(hipEventCreate(&e1));
-        launch_gemm_fp8(ctx->c.dt, epi, g, a_scale, b_scale, st);
-        WM_CHECK(hipEventRecord(e0, st));
-        for (int r = 0; r < reps; r++) launch_gemm_fp8(ctx->c.dt, epi, g, a_scale, b_scale, st);
-        WM_CHECK(hipEventRecord(e1, st));
-        WM_CHECK(hipStreamSynchronize(st));
-        float t = 0;
-        WM_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = reps > 0 ? t / reps : 0.0f;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        hipStreamDestroy(st);
+        HookStream hs;
+        const GemmArgs g = gemm_plain(A8, M, K, B8, N, bias, out, N);
+        const float t = timed_ms(hs.st, reps, true, [&] { launch_gemm_fp8(ctx->c.dt, epi, g, a_scale, b_scale, hs.st); });
+        if (ms) *ms = t;
         return 0;
     });
 }
@@ -811,23 +792,17 @@ int whisper_mi355x_debug_gemm_w8(struct whisper_context* ctx, int epi, const voi
                                  const float* b_scale, int N, const float* bias, void* out, const float* ln_w,
                                  const float* ln_b, void* y) {
     return guarded(nullptr, [&]() -> int {
-        if (!ctx || !b_scale || M < 1 || M > 128 || K % 64) return -1;
+        if (!ctx || !b_scale || M < 1 || M > 128 || K % 64 || (epi == EPI_RESID && (!ln_w || !y))) return -1;
         hipSetDevice(ctx->c.device);
-        GemmArgs g{};
-        g.A = A; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
-        g.B = B8; g.bias = bias; g.M = M; g.N = N; g.K = K;
-        g.out = out; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
-        g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
+        HookBufs b;
+        HookStream hs;
+        GemmArgs g = gemm_plain(A, M, K, B8, N, bias, out, N);
         g.w8_scale = b_scale;
-        if (epi == EPI_RESID) {
-            if (!ln_w || !y) return -1;
-            g.ln_w = ln_w; g.ln_b = ln_b; g.ln_out = y;
-        }
+        if (epi == EPI_RESID) { g.ln_w = ln_w; g.ln_b = ln_b; g.ln_out = y; }
         g.splitk_ws_elems = 16L * M * N;
-        WM_CHECK(hipMalloc(&g.splitk_ws, g.splitk_ws_elems * sizeof(float)));
-        launch_gemm(ctx->c.dt, epi, g, nullptr);
-        WM_CHECK(hipDeviceSynchronize());
-        hipFree(g.splitk_ws);
+        g.splitk_ws = (float*)b.get(g.splitk_ws_elems * sizeof(float));
+        launch_gemm(ctx->c.dt, epi, g, hs.st);
+        WM_CHECK(hipStreamSynchronize(hs.st));
         return 0;
     });
 }
@@ -845,22 +820,9 @@ int whisper_mi355x_debug_attn_encoder(struct whisper_context* ctx, const void* q
     return guarded(nullptr, [&]() -> int {
         if (!ctx || B < 1 || T < 1 || d != 64 * H || (variant != 2 && variant != 6)) return -1;
         hipSetDevice(ctx->c.device);
-        hipStream_t st;
-        WM_CHECK(hipStreamCreate(&st));
-        hipEvent_t e0, e1;
-        WM_CHECK(hipEventCreate(&e0));
-        WM_CHECK(hipEventCreate(&e1));
-        launch_attn_encoder(ctx->c.dt, qkv, out, B, T, d, H, st, variant);
-        WM_CHECK(hipEventRecord(e0, st));
-        for (int r = 0; r < reps; r++) launch_attn_encoder(ctx->c.dt, qkv, out, B, T, d, H, st, variant);
-        WM_CHECK(hipEventRecord(e1, st));
-        WM_CHECK(hipStreamSynchronize(st));
-        float t = 0;
-        WM_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = reps > 0 ? t / reps : 0.0f;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        hipStreamDestroy(st);
+        HookStream hs;
+        const float t = timed_ms(hs.st, reps, true, [&] { launch_attn_encoder(ctx->c.dt, qkv, out, B, T, d, H, hs.st, variant); });
+        if (ms) *ms = t;
         return 0;
     });
 }
@@ -871,30 +833,15 @@ int whisper_mi355x_debug_gemm_ln(struct whisper_context* ctx, const void* A, int
     return guarded(nullptr, [&]() -> int {
         if (!ctx || M > 128) return -1;
         hipSetDevice(ctx->c.device);
-        hipStream_t st;
-        WM_CHECK(hipStreamCreate(&st));
-        GemmArgs g{};
-        g.A = A; g.a_rpb = M; g.a_bstride = 0; g.a_rstride = K;
-        g.B = B; g.bias = bias; g.M = M; g.N = N; g.K = K;
-        g.out = x; g.ldo = N; g.o_rpb = M; g.o_bstride = 0; g.o_off = 0;
-        g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
+        HookBufs b;
+        HookStream hs;
+        GemmArgs g = gemm_plain(A, M, K, B, N, bias, x, N);
         g.ln_w = ln_w; g.ln_b = ln_b; g.ln_out = y;
         g.splitk_ws_elems = 64L * M * N;
-        WM_CHECK(hipMalloc(&g.splitk_ws, g.splitk_ws_elems * sizeof(float)));
-        hipEvent_t e0, e1;
-        WM_CHECK(hipEventCreate(&e0));
-        WM_CHECK(hipEventCreate(&e1));
-        WM_CHECK(hipEventRecord(e0, st));
-        for (int r = 0; r < std::max(1, reps); r++) launch_gemm(ctx->c.dt, EPI_RESID, g, st);
-        WM_CHECK(hipEventRecord(e1, st));
-        WM_CHECK(hipStreamSynchronize(st));
-        float t = 0;
-        WM_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = t / std::max(1, reps);
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        hipStreamDestroy(st);
-        hipFree(g.splitk_ws);
+        g.splitk_ws = (float*)b.get(g.splitk_ws_elems * sizeof(float));
+        // (x is updated in place by every launch: no warm launch, and at least one)
+        const float t = timed_ms(hs.st, std::max(1, reps), false, [&] { launch_gemm(ctx->c.dt, EPI_RESID, g, hs.st); });
+        if (ms) *ms = t;
         return 0;
     });
 }
@@ -910,46 +857,22 @@ int whisper_mi355x_debug_xattn(struct whisper_context* ctx, const void* enc, con
         const DType dt = ctx->c.dt;
         const int H = d / 64;
         if (splits <= 0) splits = xattn_splits(n, n_ctx);
-        void* qx = nullptr;
-        float *op = nullptr, *ml = nullptr;
-        WM_CHECK(hipMalloc(&qx, (size_t)n * 2 * H * d * 2));
-        WM_CHECK(hipMalloc((void**)&op, (size_t)n * splits * H * d * 4));
-        WM_CHECK(hipMalloc((void**)&ml, (size_t)n * splits * H * 2 * 4));
-        hipStream_t st;
-        WM_CHECK(hipStreamCreate(&st));
-        auto run = [&] {
-            launch_xattn_qproj(dt, q, wkt, n, d, H, scale, qx, st);
-            launch_xattn_step(dt, enc, slot, qx, n, n_ctx, d, splits, rescale_thr, op, ml, st);
-            launch_xattn_combine(dt, op, ml, splits, wv, bv, n, d, H, out, st);
-        };
-        hipEvent_t e0, e1;
-        WM_CHECK(hipEventCreate(&e0));
-        WM_CHECK(hipEventCreate(&e1));
-        run();
-        WM_CHECK(hipEventRecord(e0, st));
-        for (int r = 0; r < reps; r++) run();
-        WM_CHECK(hipEventRecord(e1, st));
-        WM_CHECK(hipStreamSynchronize(st));
-        float t = 0;
-        WM_CHECK(hipEventElapsedTime(&t, e0, e1));
-        if (ms) *ms = reps > 0 ? t / reps : 0.0f;
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        hipStreamDestroy(st);
-        hipFree(qx);
-        hipFree(op);
-        hipFree(ml);
+        HookBufs b;
+        HookStream hs;
+        void* qx = b.get((size_t)n * 2 * H * d * 2);
+        float* op = (float*)b.get((size_t)n * splits * H * d * 4);
+        float* ml = (float*)b.get((size_t)n * splits * H * 2 * 4);
+        const float t = timed_ms(hs.st, reps, true, [&] {
+            launch_xattn_qproj(dt, q, wkt, n, d, H, scale, qx, hs.st);
+            launch_xattn_step(dt, enc, slot, qx, n, n_ctx, d, splits, rescale_thr, op, ml, hs.st);
+            launch_xattn_combine(dt, op, ml, splits, wv, bv, n, d, H, out, hs.st);
+        });
+        if (ms) *ms = t;
         return 0;
     });
 }
 
 // ---- decoder attention (kernels/attn.hip) on caller data: one launch each, all device pointers ----------
-// the hook's stream, destroyed also when the launcher refuses the shape (WM_FAIL throws)
-struct HookStream {
-    hipStream_t st = nullptr;
-    HookStream() { WM_CHECK(hipStreamCreate(&st)); }
-    ~HookStream() { hipStreamDestroy(st); }
-};
 // slabs [splits][n][3d] f32 (q | k | v partial sums), bias [3d] f32 or null, cache
 // [slots][L][2][H][n_ctx][64] in the context dtype (K[pos], V[pos] are written), slot / pos [n] int -> out [n][d]
 int whisper_mi355x_debug_attn_self_step(struct whisper_context* ctx, const float* slabs, int splits, const float* bias,
@@ -985,17 +908,6 @@ int whisper_mi355x_debug_attn_cross_step(struct whisper_context* ctx, const floa
     });
 }
 // ---- beam search's kernels on caller data (kernels/logits.hip top-k forms, kernels/beam.hip) ---------------------
-// device buffers of a hook, freed also when a launcher throws
-struct HookBufs {
-    std::vector<void*> p;
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        WM_CHECK(hipMalloc(&q, bytes));
-        p.push_back(q);
-        return q;
-    }
-    ~HookBufs() { for (void* q : p) hipFree(q); }
-};
 static_assert(sizeof(whisper_mi355x_cand) == sizeof(TokOut), "whisper_mi355x_cand mirrors TokOut");
 int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* logits, int n, const int* rules,
                                      const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,

@@ -616,15 +616,6 @@ static void compute_energy(whisper_state* s, const float* const* pcm, const int*
 }
 
 // ---- encoder + cross KV ---------------------------------------------------------------------------
-static GemmArgs gemm_plain(const void* A, int M, int K, const void* B, int N, const float* bias, void* out, long ldo) {
-    GemmArgs g{};
-    g.A = A; g.a_rpb = M > 0 ? M : 1; g.a_bstride = 0; g.a_rstride = K;
-    g.B = B; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.out = out; g.ldo = ldo; g.o_rpb = M > 0 ? M : 1; g.o_bstride = 0; g.o_off = 0;
-    g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
-    return g;
-}
-
 // fp8 mode, decoder half: WHISPER_MI355X_FP8_DEC=1 (read when a context first quantizes its weights).
 // Off by default: correct (tests/test_gpu_fp8.py) but slower, because the decode-step GEMMs are
 // latency-bound, not bound by their weight bytes (profiles/r02_fp8_decoder_ab.txt: large-v3 fp8 at
@@ -2363,14 +2354,19 @@ static bool pipe_ok(Sched& S, const std::vector<int>& act) {
 // Everything about a decode step of n rows that can change a row's bits with n: the path (persistent step,
 // small-M GEMMs, launch chain), the cache-form cross-attention kernel (the wide one up to
 // attn_cross_wide_max() rows), the direct form's key-split count (xattn_splits), the logits GEMM's kernel
-// (gemm.hip launch_t: the unsplit 64-row kernel up to 64 rows, gemm_dec_kernel above) and the number of
-// 128-row groups (dec_groups). Equal keys: a row's results at n and at n' rows are the same bits.
+// (gemm_plan: gemm_kernel's 64-row tile up to 64 rows; above, rows 65..80 take gemm_dec_kernel unsplit and
+// rows 81..128 gemm_glds_kernel, which give a row the same bits, so that boundary is not in the key:
+// tests/test_gpu_kernels.py test_logits_gemm_rows_80_81_bitwise) and the number of 128-row groups
+// (dec_groups). Equal keys: a row's results at n and at n' rows are the same bits.
 static long step_variant(Context* c, whisper_state* s, int n) {
     const int pd = pdec_use(c, s, n, s->direct) ? 1 : 0;
     const bool small = n <= small_rows_max(c);  // deliberately coarser than step_plan's test (no w8, no gemm_small_ok)
     const bool wide = !s->direct && n <= attn_cross_wide_max();
     const int sp = s->direct ? xattn_splits(n, enc_ctx(c, s)) : 0;
-    const bool lg64 = n <= 64;
+    const Workspace& w = s->ws;
+    const GemmPlan lg = gemm_plan(GemmShape{EPI_F32, n, c->hp.n_vocab, c->hp.n_text_state, w.splitk != nullptr, w.splitk_elems,
+                                            false, false, false}, current_knobs());
+    const bool lg64 = lg.kernel == GK_REG && lg.bm == 64;
     return pd | (long)small << 2 | (long)wide << 3 | (long)sp << 4 | (long)lg64 << 9 | (long)dec_groups(n) << 10;
 }
 

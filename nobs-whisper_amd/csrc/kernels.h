@@ -4,6 +4,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace wm {
 
@@ -38,16 +39,7 @@ void launch_embed_ln(DType dt, const void* tok_emb, bool te_f32, const float* po
                      int n, int D, float* x, const float* w, const float* b, void* y, hipStream_t st);
 
 // ---- GEMM (kernels/gemm.hip): C[M][N] = A[M][K] . B[N][K]^T + bias, fused epilogues --------------
-enum Epi : int {
-    EPI_STORE = 0,     // T out[orow][n] = (v) * colscale(n)
-    EPI_GELU = 1,      // T out = gelu_ggml(v)   (ggml's f16 GELU table)
-    EPI_RESID = 2,     // f32 out[orow][n] = v + out[orow][n]            (residual stream, in place)
-    EPI_GELU_POS = 3,  // f32 out = gelu_ggml(v) + pos[m % pos_rows][n]   (conv2 + positional emb)
-    EPI_F32 = 4,       // f32 out = v                                       (logits)
-    EPI_CROSSKV = 5,   // T scatter into cross cache [slot][L][2][H][ctx][64]; K columns scaled; row m = (window m / rpw, t = m % rpw)
-    EPI_QKV_DEC = 6,   // n<d: T q[m][n]*scale ; d<=n<2d: K cache (scaled) ; 2d<=n<3d: V cache
-    EPI_GELU_F = 7,    // T out = tanh-GELU by formula in f32 (fp8 mode, and bf16 encoders: not ggml's f16 table)
-};
+// (enum Epi, the epilogue ids, and gemm_plan, what a shape will run: gemm_plan.h)
 
 // GGML block-quantized weight matrix [N][K] (the app's catalog ships q5_0 / q5_1
 // files, model.rs:153-186) kept in HBM as the file's blocks, regrouped by field (same bits, same bytes):
@@ -95,7 +87,19 @@ struct GemmArgs {
     unsigned long long* stamps;
 };
 extern unsigned long long* g_gemm_stamps;
+// out[M][ldo] = A[M][K] . B[N][K]^T + bias on contiguous rows, nothing scaled: the call every other one starts from
+inline GemmArgs gemm_plain(const void* A, int M, int K, const void* B, int N, const float* bias, void* out, long ldo) {
+    GemmArgs g{};
+    g.A = A; g.a_rpb = M > 0 ? M : 1; g.a_bstride = 0; g.a_rstride = K;
+    g.B = B; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    g.out = out; g.ldo = ldo; g.o_rpb = M > 0 ? M : 1; g.o_bstride = 0; g.o_off = 0;
+    g.sc_div = 0; g.sc_mod = 1; g.sc_lim = 0; g.scale = 1.0f;
+    return g;
+}
 
+// the plan's knobs as the launchers see them now (whisper_mi355x_set_gemm_variant / _dec_splits / _dec_bm and the
+// environment), for callers that ask gemm_plan what a shape will run
+GemmKnobs current_knobs();
 void launch_gemm(DType dt, int epi, const GemmArgs& a, hipStream_t st);
 // fp8 (OCP e4m3) operands with per-row f32 scales: C = (A8 . B8^T) * a_scale[m] * b_scale[n], then
 // the epilogue (EPI_STORE / EPI_GELU / EPI_GELU_F / EPI_RESID); K % 128 == 0, N % 16 == 0. A/B strides

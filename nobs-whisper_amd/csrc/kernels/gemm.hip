@@ -18,7 +18,7 @@
 // Roofline: MFMA-bound for the encoder/cross-KV/prefill shapes (M = B*1500), HBM-bound on the
 // weights for decode steps (M = number of active sequences).
 //
-// The GEMM kernels, and what launch_t runs them for:
+// The GEMM kernels:
 //   gemm8p_kernel      256x256 phase-interleaved LDS-DMA tiles: the big shapes (encoder, cross K/V, prefill)
 //   gemm8p_mx_kernel   the same schedule on e4m3 operands with row scales (launch_gemm_fp8)
 //   gemm_glds_kernel   128x128 LDS-DMA tiles: big shapes the 256^2 rule leaves out (and variant 1)
@@ -26,6 +26,24 @@
 //   gemm_small_kernel  decode steps of <= 32 clips, no split-K slab (launch_gemm_small)
 //   gemm_kernel        register-staged fallback for every other shape (K % 64 != 0, no workspace, variant 0)
 // with splitk_reduce_kernel / splitk_reduce_resid_ln_kernel / splitk_reduce_resid_ln4_kernel after the split ones.
+//
+// Shape -> kernel of launch_gemm, as gemm_plan (../gemm_plan.cpp) decides it at the default knobs. big: M * N >= 2^22;
+// ws: the call has a split-K workspace; s: the decode split count (dec_splits_for: by N and K only, 1..12, the
+// largest with <= 256 workgroups and >= 2 K-tiles per chunk) when its s * M * N slabs fit the workspace.
+//   1. big, K % 64 == 0, M >= 1024, N % 256 == 0 or N >= 1024   gemm8p_kernel 256x256
+//   2. big, K % 64 == 0, otherwise                              gemm_glds_kernel 128x128
+//   3. big, K % 64 != 0                                         gemm_kernel 128x128
+//   4. not big, ws, K % 64 == 0 (fused LayerNorm: M <= 128), the slabs fit:
+//        s >= 2 or fused LayerNorm      gemm_dec_kernel split, then splitk_reduce_resid_ln4_kernel (fused LayerNorm;
+//                                       _ln_ when N % 4 != 0 or N > 4096) or splitk_reduce_kernel
+//        s == 1, M > 64 (or e4m3)       gemm_dec_kernel over the whole K, no reduce (logits GEMM of 65..80 rows)
+//        s == 1, M <= 64                row 5 (logits GEMM of a small step)
+//   5. not big, ws, M <= 128, not row 4                         gemm_kernel 64x64 (M <= 64) or 128x64, split-K with
+//                                                               splitk_reduce_kernel / _resid_ln_kernel where it pays
+//   6. everything else                                          gemm_kernel 64x64, split-K where ws
+// e4m3 weights are for row 4 (M <= 128: a call that cannot get there fails); a fused LayerNorm runs on rows 4 and 5
+// only (row 6 fails with one). A split launch of gemm_dec_kernel / gemm_kernel is always the EPI_STORE instantiation
+// (the epilogue runs in the reduce).
 #include <mutex>
 #include "../common.h"
 #include "../kernels.h"
@@ -1236,40 +1254,6 @@ __global__ void __launch_bounds__(256) gemm_dec_kernel(const GemmArgs g, const i
         }
 }
 
-// debug/tuning override: -1 auto, 0 register-staged, 1 LDS-DMA 128^2 in place of 256^2, >= 2 the 256^2
-// phase-interleaved kernel (the auto choice for big GEMMs) wherever the shape is big
-int g_gemm_variant = -1;
-unsigned long long* g_gemm_stamps = nullptr;
-
-// gemm_dec_kernel row tile: the smallest of 32 / 64 / 128 rows that holds the step (the grid's row chunks
-// stay cdiv(M, 128): a smaller tile is only taken when one tile holds every row). WHISPER_MI355X_DEC_BM (or
-// whisper_mi355x_set_dec_bm, a test hook) caps the tile from below for the A/B (128: always 128 rows, the
-// round-5 kernel). Every value gives the same bits.
-int g_dec_bm = 0;  // 0: the environment's value (default 32)
-static int dec_bm_min() {
-    static const int v = getenv("WHISPER_MI355X_DEC_BM") ? atoi(getenv("WHISPER_MI355X_DEC_BM")) : 32;
-    return g_dec_bm > 0 ? g_dec_bm : v;
-}
-template <typename T, int EPI, bool SPLIT, bool W8>
-static void launch_dec_w(const GemmArgs& g, int tiles, int splits, int kc, hipStream_t st) {
-    if (g.M <= 32 && dec_bm_min() <= 32) {
-        gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 32><<<dim3(tiles, 1, splits), 256, 0, st>>>(g, kc);
-    } else if (g.M <= 64 && dec_bm_min() <= 64) {
-        gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 64><<<dim3(tiles, 1, splits), 256, 0, st>>>(g, kc);
-    } else {
-        // 65..128 rows stay one 128-row tile: two 64-row chunks (on gridDim.y, or 8 ids apart so both land on one
-        // XCD's L2) read each weight tile twice and measured slower in the 128-clip step (decode 809 -> 832-840 ms,
-        // profiles/r06_bm_m64_ab_*.json) though some isolated shapes gained (xq 11.9 -> 10.7 us)
-        gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 128><<<dim3(tiles, cdiv(g.M, 128), splits), 256, 0, st>>>(g, kc);
-    }
-}
-// W8: the weights are e4m3 bytes (g.w8_scale set)
-template <typename T, int EPI, bool SPLIT>
-static void launch_dec(const GemmArgs& g, int tiles, int splits, int kc, hipStream_t st) {
-    if (g.w8_scale) launch_dec_w<T, EPI, SPLIT, true>(g, tiles, splits, kc, st);
-    else launch_dec_w<T, EPI, SPLIT, false>(g, tiles, splits, kc, st);
-}
-
 template <typename T, int EPI>
 __global__ void splitk_reduce_kernel(const GemmArgs g, int splits) {
     const long total = (long)g.M * g.N;
@@ -1749,159 +1733,98 @@ void launch_gemm_small(DType dt, int epi, const GemmArgs& g, bool lna, hipStream
     else launch_small_dt<bf16_t>(epi, g, lna, st);
 }
 
-int g_dec_splits = 0;  // debug/tuning override of the decode-step split count (0 = heuristic)
-static int dec_splits_override() { return g_dec_splits; }
-// decode-step split count: the largest keeping the grid <= 256 workgroups (one per CU), with chunks
-// of >= 2 K-tiles and at most 12 splits. Independent of M, so a row's sums never depend on the batch.
-// Large-v3: FC1 3 splits, QKV 4, N = d GEMMs 10, FC2 12; against the round-2 rule (the smallest count
-// reaching >= 160 workgroups, <= 8 splits) decode 844 -> 838 ms per step at 128 clips, 659 -> 654 at 64,
-// 433 -> 413 at 16 (profiles/r02_dec_fill_ab.txt). Decode-step weights are read once per step by one
-// workgroup each: non-temporal LDS-DMA (aux = 2).
-static int dec_splits_for(int tiles, int nk) {
-    int splits = 1;
-    while (tiles * (splits + 1) <= 256 && splits < 12 && (splits + 1) * 2 <= nk) splits++;
-    return splits;
+// ---- launch_gemm / launch_gemm_partials: gemm_plan (../gemm_plan.h) decides, the code below only launches ----
+// The plan's debug / tuning knobs (capi.cpp's whisper_mi355x_set_gemm_variant / _dec_splits / _dec_bm write the
+// globals; WHISPER_MI355X_DEC_BM and WHISPER_MI355X_GEMM_GM are read once per process)
+int g_gemm_variant = -1;
+int g_dec_splits = 0;
+int g_dec_bm = 0;  // 0: the environment's value (default 32)
+unsigned long long* g_gemm_stamps = nullptr;
+GemmKnobs current_knobs() {
+    static const int bm_env = getenv("WHISPER_MI355X_DEC_BM") ? atoi(getenv("WHISPER_MI355X_DEC_BM")) : 32;
+    static const int gm_env = getenv("WHISPER_MI355X_GEMM_GM") ? atoi(getenv("WHISPER_MI355X_GEMM_GM")) : -1;
+    GemmKnobs k;
+    k.variant = g_gemm_variant;
+    k.dec_splits = g_dec_splits;
+    k.dec_bm_min = g_dec_bm > 0 ? g_dec_bm : bm_env;
+    k.group_m_env = gm_env;
+    return k;
 }
-// The split plan of a gemm_dec_kernel launch (K % 64 == 0): dec_splits_for's count (or the override) as
-// chunks of whole K-tiles, kc elements each, and the number of chunks that makes. splits = 0: the slabs do
-// not fit the workspace.
-struct DecPlan { int splits, kc; };
-static DecPlan dec_plan(int N, int K, int M, long ws_elems) {
-    const int nk = K / 64;
-    int splits = dec_splits_for(cdiv(N, 64), nk);
-    if (dec_splits_override() > 0) splits = std::min(dec_splits_override(), nk);
-    const int kc = cdiv(nk, splits) * 64;
-    splits = cdiv(K, kc);
-    if ((long)splits * M * N > ws_elems) return {0, 0};
-    return {splits, kc};
+static GemmShape gemm_shape(int epi, const GemmArgs& g, bool partials) {
+    GemmShape s{};
+    s.epi = epi; s.M = g.M; s.N = g.N; s.K = g.K;
+    s.has_ws = g.splitk_ws != nullptr; s.ws_elems = g.splitk_ws_elems;
+    s.fused_ln = epi == EPI_RESID && g.ln_out != nullptr;
+    s.w8 = g.w8_scale != nullptr;  // the weights are e4m3 bytes
+    s.partials = partials;
+    return s;
 }
 
-// ln4: take the 4-columns-per-thread kernel where it applies (the register-staged path below never did, and
-// the two kernels' LayerNorm sums associate differently, so it keeps its choice)
-template <typename T>
-static void launch_reduce_resid_ln(const GemmArgs& g, int splits, hipStream_t st, bool ln4 = true) {
-    if (ln4 && g.N % 4 == 0 && g.N <= 4096 && splits <= 16) {
-        const int threads = cdiv(g.N / 4, 64) * 64;
-        splitk_reduce_resid_ln4_kernel<T><<<g.M, threads, 0, st>>>(g, splits);
-        return;
+template <typename T, int EPI, bool SPLIT, bool W8>
+static void launch_dec_w(const GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    switch (p.bm) {
+        case 32: gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 32><<<grid, p.threads, 0, st>>>(g, p.kc); break;
+        case 64: gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 64><<<grid, p.threads, 0, st>>>(g, p.kc); break;
+        default: gemm_dec_kernel<T, EPI, SPLIT, 2, W8, 128><<<grid, p.threads, 0, st>>>(g, p.kc); break;
     }
-    const int npt = cdiv(g.N, 256);
-    if (npt <= 4) splitk_reduce_resid_ln_kernel<T, 4><<<g.M, 256, 0, st>>>(g, splits);
-    else if (npt <= 8) splitk_reduce_resid_ln_kernel<T, 8><<<g.M, 256, 0, st>>>(g, splits);
-    else WM_FAIL("fused LN width %d > 2048", g.N);
 }
-
-// the plain split-K reduce of a decode step: one thread per 4 columns (N % 4 == 0), 64-thread
-// workgroups when that is under 64K threads so the work spreads over every CU (at 128 clips a d-wide
-// reduce is 41K threads: 160 busy 256-thread workgroups before, 640 of 64 now); the same bits
+// A split launch stores its partial tile into the slab and never reaches the epilogue (that runs in the reduce
+// kernel), so every split launch, here and in launch_reg, is the EPI_STORE instantiation: one kernel per tile
+// instead of one per (tile, epilogue).
 template <typename T, int EPI>
-static void launch_splitk_reduce(const GemmArgs& g, int splits, hipStream_t st) {
-    const long total = (long)g.M * g.N, work = (g.N & 3) == 0 ? total / 4 : total;
-    const int thr = work < 65536 ? 64 : 256;
-    splitk_reduce_kernel<T, EPI><<<std::min<long>(4096, cdiv(work, thr)), thr, 0, st>>>(g, splits);
+static void launch_dec(const GemmArgs& g, const GemmPlan& p, bool w8, hipStream_t st) {
+    if (p.split) {
+        if (w8) launch_dec_w<T, EPI_STORE, true, true>(g, p, st);
+        else launch_dec_w<T, EPI_STORE, true, false>(g, p, st);
+    } else {
+        if (w8) launch_dec_w<T, EPI, false, true>(g, p, st);
+        else launch_dec_w<T, EPI, false, false>(g, p, st);
+    }
 }
-
-// The encoder GEMMs' tile order (gemm8p_kernel gm). Row-major (n fastest) lets the 32 workgroups an XCD
-// runs at once cover ~1.6 m-tiles x 20 n-tiles of FC1, so every B tile is fetched by every XCD for every
-// m-tile; groups of 4 m-tiles make them a 4 x 8 block. Measured (large-v3, 128 x 30 s, rocprofv3
-// FETCH_SIZE x2, profiles/r05_gemm_gm_pmc.txt): FC1 2068 -> 1111 MB per launch, QKV 1243 -> 848 MB; the
-// d-wide GEMMs (5 n-tiles) fetched more (857 -> 987 MB), and stay row-major. The encode phase time does not
-// move (321.3 / 320.1 / 324.0 / 331.8 ms at gm 0 / 4 / 8 / 16): the kernel is bound by its MFMA / LDS
-// schedule, not by L2 misses.
-static int gemm_group_m(int tiles_n) {
-    static const int env = getenv("WHISPER_MI355X_GEMM_GM") ? atoi(getenv("WHISPER_MI355X_GEMM_GM")) : -1;
-    if (env >= 0) return env;
-    return tiles_n >= 8 ? 4 : 0;
+template <typename T, int EPI>
+static void launch_reg(const GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    if (p.split) {
+        if (p.bm == 64) gemm_kernel<T, 64, 64, 2, 2, EPI_STORE, true><<<grid, p.threads, 0, st>>>(g, p.kc);
+        else gemm_kernel<T, 128, 64, 2, 2, EPI_STORE, true><<<grid, p.threads, 0, st>>>(g, p.kc);
+    } else if (p.bn == 128) {
+        gemm_kernel<T, 128, 128, 2, 2, EPI, false><<<grid, p.threads, 0, st>>>(g, p.kc);
+    } else {
+        if (p.bm == 64) gemm_kernel<T, 64, 64, 2, 2, EPI, false><<<grid, p.threads, 0, st>>>(g, p.kc);
+        else gemm_kernel<T, 128, 64, 2, 2, EPI, false><<<grid, p.threads, 0, st>>>(g, p.kc);
+    }
+}
+template <typename T, int EPI>
+static void launch_reduce(const GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+    switch (p.reduce) {
+        case GR_NONE: break;
+        case GR_PLAIN: splitk_reduce_kernel<T, EPI><<<p.red_grid, p.red_threads, 0, st>>>(g, p.splits); break;
+        case GR_LN4: splitk_reduce_resid_ln4_kernel<T><<<p.red_grid, p.red_threads, 0, st>>>(g, p.splits); break;
+        case GR_LN:
+            if (p.red_npt == 4) splitk_reduce_resid_ln_kernel<T, 4><<<p.red_grid, p.red_threads, 0, st>>>(g, p.splits);
+            else splitk_reduce_resid_ln_kernel<T, 8><<<p.red_grid, p.red_threads, 0, st>>>(g, p.splits);
+            break;
+    }
 }
 
 template <typename T, int EPI>
 static void launch_t(const GemmArgs& g, hipStream_t st) {
-    if (g.w8_scale) {  // e4m3 weights: the decode-step split-K kernel only
-        const bool fused_ln = EPI == EPI_RESID && g.ln_out != nullptr;
-        if (!(g.splitk_ws && g.M <= 128 && g.K % 64 == 0 && g_gemm_variant != 0 && (EPI != EPI_RESID || fused_ln))) WM_FAIL("e4m3 weights need the decode-step GEMM path (M %d <= 128, K %% 64 == 0)", g.M);
-    }
-    const bool big256 = g_gemm_variant >= 2 ||
-                        (g_gemm_variant < 0 && (g.N % 256 == 0 || g.N >= 1024) && g.M >= 1024);
-    if ((long)g.M * g.N >= 256L * 128 * 128 && g.K % 64 == 0 && big256) {
-        const int tn = cdiv(g.N, 256);
-        GemmArgs ga = g;
-        ga.stamps = g_gemm_stamps;
-        gemm8p_kernel<T, EPI><<<tn * cdiv(g.M, 256), 512, 0, st>>>(ga, tn, gemm_group_m(tn));
-        return;
-    }
-    if ((long)g.M * g.N >= 256L * 128 * 128 && g.K % 64 == 0 && g_gemm_variant != 0) {
-        const int tn = cdiv(g.N, 128);
-        gemm_glds_kernel<T, EPI><<<tn * cdiv(g.M, 128), 256, 0, st>>>(g, tn);
-        return;
-    }
-    if ((long)g.M * g.N >= 256L * 128 * 128) {
-        dim3 grid(cdiv(g.N, 128), cdiv(g.M, 128));
-        gemm_kernel<T, 128, 128, 2, 2, EPI, false><<<grid, 256, 0, st>>>(g, g.K);
-        return;
-    }
-    const bool fused_ln = EPI == EPI_RESID && g.ln_out != nullptr;
-    const int nk = cdiv(g.K, 64);
-    if (g.splitk_ws && (g.M <= 128 || !fused_ln) && g.K % 64 == 0 && g_gemm_variant != 0) {
-        // decode step and small prefill (gemm_dec_kernel; M > 128 as 128-row chunks, gridDim.y): the
-        // split count depends on N and K only (dec_splits_for), so a row's sums, and the bits of every
-        // result, do not depend on how many clips share the launch (batch == single). (Chunks of >= 5
-        // K-tiles measured faster in isolation, 9.6 vs 10.4 us at N = K = 1280, but not in the decode
-        // step: 82.0 vs 81.6 us of GEMM + reduce per layer.)
-        const int tiles = cdiv(g.N, 64);
-        const DecPlan p = dec_plan(g.N, g.K, g.M, g.splitk_ws_elems);
-        // unsplit at M <= 64 (the logits GEMM of a small batch): the 64-row register-staged kernel
-        // below wastes less of its tile (measured 23 vs 51 us at M = 16, N = 51866)
-        const bool small_unsplit = p.splits == 1 && !fused_ln && g.M <= 64 && !g.w8_scale;
-        if (g.w8_scale && !p.splits) WM_FAIL("e4m3 decode GEMM: split-K workspace too small");
-        if (p.splits && !small_unsplit) {
-            if (p.splits == 1 && !fused_ln) {
-                launch_dec<T, EPI, false>(g, tiles, 1, p.kc, st);
-                return;
-            }
-            launch_dec<T, EPI, true>(g, tiles, p.splits, p.kc, st);
-            if (fused_ln) launch_reduce_resid_ln<T>(g, p.splits, st);
-            else launch_splitk_reduce<T, EPI>(g, p.splits, st);
-            return;
+    const GemmShape sh = gemm_shape(EPI, g, false);
+    const GemmPlan p = gemm_plan(sh, current_knobs());
+    if (p.error[0]) WM_FAIL("%s", p.error);
+    switch (p.kernel) {
+        case GK_8P: {
+            GemmArgs ga = g;
+            ga.stamps = g_gemm_stamps;
+            gemm8p_kernel<T, EPI><<<p.grid_x, p.threads, 0, st>>>(ga, p.tiles_n, p.gm);
+            break;
         }
+        case GK_GLDS: gemm_glds_kernel<T, EPI><<<p.grid_x, p.threads, 0, st>>>(g, p.tiles_n); break;
+        case GK_DEC: launch_dec<T, EPI>(g, p, sh.w8, st); break;
+        case GK_REG: launch_reg<T, EPI>(g, p, st); break;
     }
-    if (g.splitk_ws && g.M <= 128) {
-        // decode step (M = active clips <= 128): one M tile, the weight stream read exactly once;
-        // K split to ~128 workgroups with >= 4 K-tiles each (partial slabs: M*N*splits*8 bytes)
-        const int BM = g.M <= 64 ? 64 : 128;
-        const int tiles = cdiv(g.N, 64);
-        int splits = std::min(std::max(1, 128 / tiles), std::max(1, nk / 4));
-        while (splits > 1 && (long)splits * g.M * g.N > g.splitk_ws_elems) splits--;
-        if (splits > 1 || fused_ln) {
-            const int kc = cdiv(cdiv(g.K, splits), 64) * 64;
-            splits = cdiv(g.K, kc);
-            dim3 grid(tiles, 1, splits);
-            if (BM == 64) gemm_kernel<T, 64, 64, 2, 2, EPI, true><<<grid, 256, 0, st>>>(g, kc);
-            else gemm_kernel<T, 128, 64, 2, 2, EPI, true><<<grid, 256, 0, st>>>(g, kc);
-            if (fused_ln) launch_reduce_resid_ln<T>(g, splits, st, false);
-            else launch_splitk_reduce<T, EPI>(g, splits, st);
-        } else {
-            dim3 grid(tiles, 1);
-            if (BM == 64) gemm_kernel<T, 64, 64, 2, 2, EPI, false><<<grid, 256, 0, st>>>(g, g.K);
-            else gemm_kernel<T, 128, 64, 2, 2, EPI, false><<<grid, 256, 0, st>>>(g, g.K);
-        }
-        return;
-    }
-    if (fused_ln) WM_FAIL("fused LN requires the decode split-K path");
-    const int tiles = cdiv(g.N, 64) * cdiv(g.M, 64);
-    int splits = std::min(16, std::max(1, 512 / tiles));
-    splits = std::min(splits, std::max(1, nk / 2));
-    while (splits > 1 && (long)splits * g.M * g.N > g.splitk_ws_elems) splits--;
-    if (!g.splitk_ws || splits <= 1) {
-        dim3 grid(cdiv(g.N, 64), cdiv(g.M, 64));
-        gemm_kernel<T, 64, 64, 2, 2, EPI, false><<<grid, 256, 0, st>>>(g, g.K);
-        return;
-    }
-    const int kc = cdiv(cdiv(g.K, splits), 64) * 64;
-    splits = cdiv(g.K, kc);
-    dim3 grid(cdiv(g.N, 64), cdiv(g.M, 64), splits);
-    gemm_kernel<T, 64, 64, 2, 2, EPI, true><<<grid, 256, 0, st>>>(g, kc);
-    const long total = (long)g.M * g.N;
-    splitk_reduce_kernel<T, EPI><<<std::min<long>(1024, cdiv(total, 256)), 256, 0, st>>>(g, splits);
+    launch_reduce<T, EPI>(g, p, st);
 }
 
 template <typename T>
@@ -1921,9 +1844,9 @@ static void launch_dt(int epi, const GemmArgs& g, hipStream_t st) {
 
 template <typename T>
 static int launch_partials_t(const GemmArgs& g, hipStream_t st) {
-    if (!g.splitk_ws || g.M > 128 || g.K % 64 != 0) return 0;
-    const DecPlan p = dec_plan(g.N, g.K, g.M, g.splitk_ws_elems);
-    if (p.splits) launch_dec<T, EPI_STORE, true>(g, cdiv(g.N, 64), p.splits, p.kc, st);
+    const GemmShape sh = gemm_shape(EPI_STORE, g, true);
+    const GemmPlan p = gemm_plan(sh, current_knobs());
+    if (p.splits) launch_dec<T, EPI_STORE>(g, p, sh.w8, st);
     return p.splits;
 }
 

@@ -309,3 +309,31 @@ def test_dec_gemm_row_tiles_bitwise(wrs, micro_model, M):
                 assert np.isfinite(outs[1].astype(np.float32)).all()
         finally:
             c.close()
+
+
+def test_logits_gemm_rows_80_81_bitwise(wrs, micro_model):
+    """A logits GEMM (f32 out, N = 51866, K = 384, bias) gives a row the same bits whichever kernel its row count picks
+    above 64 rows: 65 and 80 rows run gemm_dec_kernel unsplit, 81 and 128 rows gemm_glds_kernel (M * N reaches 2^22;
+    tests/test_gemm_plan.py pins the kernels). Both take the whole K in 64-wide tiles of two 32-deep MFMA steps. The
+    pipelined decoder accepts a speculative step's rows across the 80 | 81 boundary on this (engine.cpp step_variant
+    keys the logits GEMM on the 64-row boundary only)."""
+    N, K = 51866, 384
+    rng = np.random.default_rng(8081)
+    A32 = rng.standard_normal((128, K), dtype=np.float32)
+    B32 = rng.standard_normal((N, K), dtype=np.float32) / np.float32(np.sqrt(K))
+    bias = rng.standard_normal(N).astype(np.float32)
+    for dt in (wrs.F16, wrs.BF16):
+        if dt == wrs.F16:
+            A, B = A32.astype(np.float16), B32.astype(np.float16)
+        else:
+            A, B = _to_bf16_bits(A32)[0], _to_bf16_bits(B32)[0]
+        c = wrs.WhisperContext(micro_model, dtype=dt)
+        try:
+            out = {M: _run_gemm(wrs, c, np.ascontiguousarray(A[:M]), B, bias, -1, epi=4)[0] for M in (80, 81, 128, 65)}
+        finally:
+            c.close()
+        assert np.isfinite(out[80]).all() and np.abs(out[80]).max() > 1.0, dt
+        for M in (81, 128, 65):
+            rows = min(M, 80)
+            diff = out[M][:rows].view(np.uint32) != out[80][:rows].view(np.uint32)
+            assert not diff.any(), f"dtype {dt}: {int(diff.sum())} of {diff.size} outputs of rows 0..{rows - 1} differ between {M} and 80 rows"
