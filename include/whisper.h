@@ -35,8 +35,14 @@
  * whisper_full_params.token_timestamps, thold_pt, thold_ptsum, max_len and split_on_word are implemented (DESIGN.md §13,
  * whisper_mi355x.h). whisper_full_params.audio_ctx is implemented: the encoder, the cross K/V and every cross
  * attention of the call work on the first audio_ctx positions of each window; <= 0 = the model's n_audio_ctx, a value
- * above it makes whisper_full* return -5 (whisper_mi355x.h). Still accepted and ignored: suppress_nst,
- * suppress_regex, the grammar fields, tdrz_enable and vad (with vad_model_path and vad_params).
+ * above it makes whisper_full* return -5 (whisper_mi355x.h).
+ *
+ * whisper_full_params.suppress_nst and suppress_regex are implemented (whisper_mi355x.h): the tokens of
+ * upstream's non-speech list, and every token whose whole string the pattern matches (std::regex, ECMAScript; NULL =
+ * off), get a logit of -inf in every decoding mode. A pattern that does not compile makes whisper_full* return -8
+ * before anything is encoded, with one line on stderr (upstream throws std::regex_error).
+ *
+ * Still accepted and ignored: the grammar fields, tdrz_enable and vad (with vad_model_path and vad_params).
  */
 #ifndef WHISPER_H
 #define WHISPER_H

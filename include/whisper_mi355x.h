@@ -394,6 +394,27 @@ WHISPER_API int whisper_mi355x_debug_decode_advance(struct whisper_context * ctx
                                                     struct whisper_mi355x_seq_ctl * ctl, const unsigned * err,
                                                     struct whisper_mi355x_cand * ring, unsigned * ring_err);
 
+/* The deny mask of whisper_full_params.suppress_nst / suppress_regex (whisper.h) for this context's vocabulary, as
+ * whisper_full* builds it, from the context's one-entry cache. Host only: nothing touches the device.
+ * words (cap_words >= (n_vocab + 31) / 32) receives the mask: token i is bit i & 31 of word i >> 5, set = the
+ * token's logit becomes -inf before the softmax; bits at and above n_vocab are 0. regex = NULL: no pattern (an empty
+ * string is a pattern like any other). Returns the word count, -1 on bad arguments (null ctx or words, cap_words too
+ * small), -8 when the pattern does not compile (one stderr line; words is not written).
+ * whisper_mi355x_suppress_builds: masks built (not taken from the cache) since the context was created. */
+WHISPER_API int  whisper_mi355x_suppress_mask(struct whisper_context * ctx, bool suppress_nst, const char * regex,
+                                              uint32_t * words, int cap_words);
+WHISPER_API long whisper_mi355x_suppress_builds(struct whisper_context * ctx);
+/* Debug: whisper_mi355x_debug_logits / whisper_mi355x_debug_logits_topk with a deny mask: deny = host
+ * [(n_vocab + 31) / 32] words as above, uploaded and given to the launches, or NULL: the launches of the hooks
+ * without _deny, bit for bit. */
+WHISPER_API int whisper_mi355x_debug_logits_deny(struct whisper_context * ctx, const float * logits, int n,
+                                                 const struct whisper_mi355x_seq_ctl * ctl, int form,
+                                                 struct whisper_mi355x_cand * out, float * probs, const uint32_t * deny);
+WHISPER_API int whisper_mi355x_debug_logits_topk_deny(struct whisper_context * ctx, const float * logits, int n,
+                                                      const int * rules, const float * temperature, int k, int split,
+                                                      struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy,
+                                                      const uint32_t * deny);
+
 /* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
  * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.
  * scores: q [n_text_layer][sum n_rows][d] (device, compute type: the cross-Q rows of every layer, already scaled

@@ -10,6 +10,7 @@
 
 #include "../../include/whisper_mi355x.h"
 #include "engine.h"
+#include "suppress.h"
 
 namespace wm { extern int g_gemm_variant; extern int g_dec_splits; extern int g_dec_bm; extern unsigned long long* g_gemm_stamps; }
 using namespace wm;
@@ -909,9 +910,22 @@ int whisper_mi355x_debug_attn_cross_step(struct whisper_context* ctx, const floa
 }
 // ---- beam search's kernels on caller data (kernels/logits.hip top-k forms, kernels/beam.hip) ---------------------
 static_assert(sizeof(whisper_mi355x_cand) == sizeof(TokOut), "whisper_mi355x_cand mirrors TokOut");
+// the deny mask of a hook on the device (null stays null: the launch without a mask)
+static const uint32_t* hook_deny(HookBufs& b, const uint32_t* deny, int n_vocab, hipStream_t st) {
+    if (!deny) return nullptr;
+    const size_t bytes = (size_t)suppress_words(n_vocab) * sizeof(uint32_t);
+    uint32_t* d = (uint32_t*)b.get(bytes);
+    WM_CHECK(hipMemcpyAsync(d, deny, bytes, hipMemcpyHostToDevice, st));
+    return d;
+}
 int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* logits, int n, const int* rules,
                                      const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,
                                      struct whisper_mi355x_cand* greedy) {
+    return whisper_mi355x_debug_logits_topk_deny(ctx, logits, n, rules, temperature, k, split, cand, greedy, nullptr);
+}
+int whisper_mi355x_debug_logits_topk_deny(struct whisper_context* ctx, const float* logits, int n, const int* rules,
+                                          const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,
+                                          struct whisper_mi355x_cand* greedy, const uint32_t* deny) {
     return guarded(nullptr, [&]() -> int {
         if (!ctx || !logits || !rules || !cand || !greedy || n <= 0 || k < 1 || k > kTopkMax) return -1;
         hipSetDevice(ctx->c.device);
@@ -928,8 +942,9 @@ int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* l
         TokOut* d_out = (TokOut*)b.get((size_t)n * (kTopkMax + 1) * sizeof(TokOut));
         void* rec = split ? b.get(logits_rec_bytes(n)) : nullptr;
         WM_CHECK(hipMemcpyAsync(d_ctl, ctl.data(), n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
-        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out + (size_t)n * kTopkMax, nullptr, rec, st);
-        launch_logits_topk(logits, V, d_ctl, n, ctx->c.vid, d_out, k, rec, st);
+        const uint32_t* d_deny = hook_deny(b, deny, V, st);
+        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out + (size_t)n * kTopkMax, nullptr, rec, d_deny, st);
+        launch_logits_topk(logits, V, d_ctl, n, ctx->c.vid, d_out, k, rec, d_deny, st);
         std::vector<TokOut> out((size_t)n * (kTopkMax + 1));
         WM_CHECK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         WM_CHECK(hipStreamSynchronize(st));
@@ -1046,11 +1061,32 @@ int whisper_mi355x_debug_token_vad(struct whisper_context* ctx, const float* ene
         return 0;
     });
 }
+// ---- the deny mask of suppress_nst / suppress_regex (suppress.h; host only) ------------------------------------------
+int whisper_mi355x_suppress_mask(struct whisper_context* ctx, bool suppress_nst, const char* regex, uint32_t* words,
+                                 int cap_words) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !words || cap_words < suppress_words(ctx->c.hp.n_vocab)) return -1;
+        std::vector<uint32_t> w;
+        if (const int r = deny_lookup(&ctx->c, suppress_nst, regex, &w)) return r;
+        memcpy(words, w.data(), w.size() * sizeof(uint32_t));
+        return (int)w.size();
+    });
+}
+long whisper_mi355x_suppress_builds(struct whisper_context* ctx) {
+    if (!ctx) return 0;
+    std::lock_guard<std::mutex> lk(ctx->c.deny_mu);
+    return ctx->c.deny_builds;
+}
 // ---- the greedy logits kernels and the step advance on caller data (kernels/logits.hip) --------------------------
 static_assert(sizeof(whisper_mi355x_seq_ctl) == sizeof(SeqCtl), "whisper_mi355x_seq_ctl mirrors SeqCtl");
 int whisper_mi355x_debug_logits(struct whisper_context* ctx, const float* logits, int n,
                                 const struct whisper_mi355x_seq_ctl* ctl, int form, struct whisper_mi355x_cand* out,
                                 float* probs) {
+    return whisper_mi355x_debug_logits_deny(ctx, logits, n, ctl, form, out, probs, nullptr);
+}
+int whisper_mi355x_debug_logits_deny(struct whisper_context* ctx, const float* logits, int n,
+                                     const struct whisper_mi355x_seq_ctl* ctl, int form, struct whisper_mi355x_cand* out,
+                                     float* probs, const uint32_t* deny) {
     return guarded(nullptr, [&]() -> int {
         if (!ctx || !logits || !ctl || !out || n <= 0 || form < 0 || form > 1) return -1;
         for (int r = 0; r < n; r++)
@@ -1067,7 +1103,7 @@ int whisper_mi355x_debug_logits(struct whisper_context* ctx, const float* logits
         void* rec = form ? b.get(logits_rec_bytes(n)) : nullptr;
         WM_CHECK(hipMemcpyAsync(d_ctl, ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
         if (d_probs) WM_CHECK(hipMemsetAsync(d_probs, 0xff, pbytes, st));  // rows the kernel leaves alone read as NaN
-        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out, d_probs, rec, st);
+        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out, d_probs, rec, hook_deny(b, deny, V, st), st);
         WM_CHECK(hipGetLastError());
         WM_CHECK(hipMemcpyAsync(out, d_out, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         if (d_probs) WM_CHECK(hipMemcpyAsync(probs, d_probs, pbytes, hipMemcpyDeviceToHost, st));

@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "engine.h"
+#include "suppress.h"
 #include "token_times.h"
 
 namespace wm {
@@ -190,6 +191,7 @@ static void reset_for_reuse(whisper_state* s) {
     s->pdec_off_until = 0;
     s->pdec_off = false;
     s->mode = StepMode{};
+    s->deny_on = false;
     s->beam_info.clear();
     s->sample_seed = 0;
     s->cand_info.clear();
@@ -317,7 +319,7 @@ static void free_ws(Workspace& w) {
     dfree(w.pcm); dfree(w.mel); dfree(w.mel_ptrs); dfree(w.splitk); dfree(w.enc); dfree(w.qx); dfree(w.xo);
     dfree(w.xml); dfree(w.kvslot); dfree(w.hs); dfree(w.qtiles); dfree(w.wdq); dfree(w.pd_sync);
     dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage); dfree(w.sctr);
-    dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans);
+    dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans); dfree(w.deny);
     if (w.h_sslot) hipHostFree(w.h_sslot);
     if (w.h_sctr) hipHostFree(w.h_sctr);
     if (w.h_cand) hipHostFree(w.h_cand);
@@ -395,6 +397,7 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips
     const size_t d = hp.n_audio_state, nm = hp.n_mels, T = hp.n_audio_ctx, E = esize(c->dt);
     const int n_enc = std::min(n_clips, enc_batch());
     if (n_enc > w.cap_enc || n_jobs > w.cap_jobs) drop_graphs(s);
+    if (!w.deny) dalloc(w.deny, (size_t)suppress_words(hp.n_vocab) * sizeof(uint32_t));  // (kept when the workspace grows)
     if (n_enc > w.cap_enc) {
         dfree(w.mel_img); dfree(w.h1); dfree(w.hn); dfree(w.qkv); dfree(w.att); dfree(w.ff); dfree(w.x);
         dfree(w.win_job); dfree(w.hs);
@@ -2133,13 +2136,14 @@ static bool ctl_upload(Sched& S, int n) {
 }
 static void logits_launch(Context* c, whisper_state* s, int n) {
     Workspace& w = s->ws;
+    const uint32_t* deny = s->deny_on ? w.deny : nullptr;  // suppress_nst / suppress_regex (deny_prepare)
     if (s->mode.topk > 0) {  // a beam step: top-k candidates per row (candidate 0 = the greedy record of the row)
         KT kt(s, K_TOPK, (double)n * c->hp.n_vocab * 4);
-        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->mode.topk, w.lrec, s->stream);
+        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->mode.topk, w.lrec, deny, s->stream);
         return;
     }
     KT kt(s, K_LOGITS, (double)n * c->hp.n_vocab * 4);
-    launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.tout, w.probs, w.lrec, s->stream);
+    launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.tout, w.probs, w.lrec, deny, s->stream);
 }
 static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vector<float>>& probs_rows) {
     Context* c = S.c;
@@ -2211,11 +2215,12 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     }
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
-            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && (!s->mode.sample || g.seed == s->sample_seed))
+            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && g.deny == s->deny_on && (!s->mode.sample || g.seed == s->sample_seed))
             return &g;
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
     g.seed = s->sample_seed;  // (a kernel argument of the draw below)
     g.actx = enc_ctx(c, s);
+    g.deny = s->deny_on;
     hipGraph_t graph;
     s->capture_ev = &g.ev;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -3126,12 +3131,59 @@ static void publish(Sched& S) {
     S.c->timings.prompt_ms += (float)S.t_prefill;
 }
 
+// ---- the deny mask of suppress_nst / suppress_regex (suppress.h) ---------------------------------------
+int deny_lookup(Context* c, bool suppress_nst, const char* regex, std::vector<uint32_t>* words) {
+    Context::DenyKey key;
+    key.nst = suppress_nst;
+    key.has_regex = regex != nullptr;
+    if (regex) key.regex = regex;
+    std::lock_guard<std::mutex> lk(c->deny_mu);
+    if (!c->deny_cached || !(c->deny_key == key)) {
+        std::vector<uint32_t> built;
+        std::string err;
+        if (suppress_build(c->vocab.token_to_id, c->hp.n_vocab, suppress_nst, regex, built, &err) != 0) {
+            fprintf(stderr, "whisper_mi355x: suppress_regex '%s' does not compile: %s\n", regex, err.c_str());
+            return -8;  // (the cached mask stays)
+        }
+        c->deny_words.swap(built);
+        c->deny_key = key;
+        c->deny_cached = true;
+        c->deny_builds++;
+    }
+    if (words) *words = c->deny_words;
+    return 0;
+}
+
+// The call's mask into the state's buffer, on its stream, before the first logits launch: nothing when the call has
+// no mask, or when the buffer holds this key's words already. (After ensure_ws: the buffer exists.) 0 or -8.
+static int deny_prepare(Context* c, whisper_state* s, const whisper_full_params& p) {
+    Workspace& w = s->ws;
+    Context::DenyKey key;
+    key.nst = p.suppress_nst;
+    key.has_regex = p.suppress_regex != nullptr;
+    if (p.suppress_regex) key.regex = p.suppress_regex;
+    s->deny_on = key.on();
+    if (!s->deny_on || (w.deny_held && w.deny_key == key)) return 0;
+    std::vector<uint32_t> words;
+    if (const int r = deny_lookup(c, p.suppress_nst, p.suppress_regex, &words)) return r;
+    w.deny_held = false;
+    WM_CHECK(hipMemcpyAsync(w.deny, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    WM_CHECK(hipStreamSynchronize(s->stream));  // (`words` goes out of scope; once per change of key)
+    w.deny_key = key;
+    w.deny_held = true;
+    return 0;
+}
+
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                           int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
     WM_CHECK(hipSetDevice(c->device));
     Sched S;
     S.c = c; S.s = s; S.p = p; S.o = o; S.single_api = single_api;
     if (const int r = check_args(S, n_jobs)) return r;
+    s->deny_on = false;
+    // a pattern that does not compile ends the call before anything is encoded (the mask is cached for deny_prepare)
+    if (p.suppress_nst || p.suppress_regex)
+        if (const int r = deny_lookup(c, p.suppress_nst, p.suppress_regex, nullptr)) return r;
     ensure_expanded(c, s->stream);  // quantized files: before anything is captured
     S.hyps.resize(S.beam_k > 0 || S.sample_n > 1 ? n_jobs : 0);
     s->beam_info.assign(n_jobs, {});
@@ -3150,6 +3202,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
         s->direct = S.beam_k > 1 ? false : pick_direct(c, n_jobs);
         ensure_ws(c, s, n_jobs * std::max(1, std::max(S.beam_k, S.sample_n)), n_jobs);
         if (!single_api) s->audio_ctx = 0;  // every clip of the batch API starts as on a fresh state (apply_audio_ctx)
+        if (const int r = deny_prepare(c, s, p)) return r;
         compute_mel(c, s, pcm, n, n_jobs, on_device);
     }
     if (p.token_timestamps) { ScopeTimer timed{S.t_tokts}; compute_energy(s, pcm, n, n_jobs, on_device); }
@@ -3175,6 +3228,8 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
                int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
     if (single_api || n_jobs <= kPairMin) return full_batch_one(c, s, p, pcm, n, n_jobs, on_device, o, single_api);
     if (const int r = check_audio_ctx(c, p.audio_ctx)) return r;  // (before the halves start: one line, not one per half)
+    if (p.suppress_nst || p.suppress_regex)
+        if (const int r = deny_lookup(c, p.suppress_nst, p.suppress_regex, nullptr)) return r;
     WM_CHECK(hipSetDevice(c->device));
     if (!s->twin) s->twin = create_state(c);
     whisper_state* t = s->twin;

@@ -133,6 +133,20 @@ struct Context {
     void* dtw_heads_dev = nullptr;  // int2 {head, index in dtw_heads} grouped by layer (dtw_layer_first)
     std::vector<int> dtw_layer_first;  // [n_text_layer + 1]: layer l's entries of dtw_heads_dev
     int dtw_last_layer = -1;
+    // The deny mask of the last (suppress_nst, suppress_regex) asked for (suppress.h): matching the
+    // whole vocabulary with std::regex costs milliseconds, so a call whose key equals the cached one rebuilds nothing.
+    // States on different threads share it under the mutex and copy the words out.
+    struct DenyKey {
+        bool nst = false, has_regex = false;
+        std::string regex;
+        bool on() const { return nst || has_regex; }
+        bool operator==(const DenyKey& o) const { return nst == o.nst && has_regex == o.has_regex && regex == o.regex; }
+    };
+    std::mutex deny_mu;
+    bool deny_cached = false;
+    DenyKey deny_key;
+    std::vector<uint32_t> deny_words;
+    long deny_builds = 0;  // masks built since the context was created (whisper_mi355x_suppress_builds)
 };
 
 struct TokenData {
@@ -181,6 +195,12 @@ struct Workspace {
     SeqCtl* ctl = nullptr;
     TokOut* tout = nullptr;
     void* lrec = nullptr;  // split logits kernel: per-chunk records
+    // the deny mask of suppress_nst / suppress_regex (suppress_words(n_vocab) words; allocated with the first
+    // workspace and kept until the state goes, so its address can be a kernel argument of captured steps) and the
+    // key of the mask it holds
+    uint32_t* deny = nullptr;
+    bool deny_held = false;
+    Context::DenyKey deny_key;
     int *win_job = nullptr, *win_seek = nullptr, *win_slot = nullptr;
     // persistent decode step: the hand-off block (granules + error word) and the error word's host copy
     unsigned* pd_sync = nullptr;
@@ -306,7 +326,9 @@ struct whisper_state {
     // draw's key)
     // (actx: the encoder positions of the call, wm::enc_ctx: the cross-attention split counts, grid sizes and the
     // direct form's slot stride of a captured step depend on it)
-    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; };
+    // (deny: the step's logits launch reads the deny mask, whisper_state::deny_on: the pointer, or null, is a kernel
+    // argument)
+    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; bool deny = false; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
     double cur_self_work = 0;                     // self-attention bytes of the current step
@@ -321,6 +343,8 @@ struct whisper_state {
     // the mode of the step that is running (a beam step, a sampled step, the prefill's top-k pass); set by
     // engine.cpp's ModeScope for that step only
     wm::StepMode mode;
+    // the current call has a deny mask (suppress_nst or suppress_regex is set): its logits launches read ws.deny
+    bool deny_on = false;
     // beam_info[job] = the beams of the job's last beam-searched window (whisper_mi355x_beam_info)
     struct BeamRec { std::vector<int> tokens; double sum_logprobs_all = 0; int flags = 0; };
     std::vector<std::vector<BeamRec>> beam_info;
@@ -370,6 +394,9 @@ struct FullOpts {
 extern std::atomic<long> g_decoded_tokens_total;
 int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                int n_jobs, bool on_device, const FullOpts& o, bool single_api);
+// The deny mask of (suppress_nst, regex) from the context's one-entry cache, built when the key differs: 0 and the
+// words in `words` (if given), or -8 and one stderr line when the pattern does not compile. Host only.
+int deny_lookup(Context* c, bool suppress_nst, const char* regex, std::vector<uint32_t>* words);
 
 // pieces exposed for whisper.h's low-level API
 int compute_mel(Context* c, whisper_state* s, const float* const* pcm, const int* n, int n_jobs, bool on_device);

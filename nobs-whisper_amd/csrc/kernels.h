@@ -315,8 +315,11 @@ struct SeqCtl {             // per-sequence inputs of whisper_process_logits
 struct TokOut { int id, tid; float p, plog, pt, ptsum, nosp_prob, pad; };
 // rec: scratch of logits_rec_bytes(n_seq) bytes for the split form (rows spread over several workgroups
 // each, used for up to 16 rows); null = one workgroup per row
+// deny: the deny mask of suppress_nst / suppress_regex on the device (suppress.h: (n_vocab + 31) / 32 words, bit
+// i & 31 of word i >> 5 = token i gets -inf like any other rule; nosp_prob stays the raw row's), or null: no mask,
+// and the launch is bit for bit the one from before the mask existed
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v,
-                   TokOut* out, float* probs, void* rec, hipStream_t st);
+                   TokOut* out, float* probs, void* rec, const uint32_t* deny, hipStream_t st);
 size_t logits_rec_bytes(int n_seq);
 // Top-k after the rules (beam search): the k <= kTopkMax most probable tokens of every row, p > 0, in
 // (p descending, id ascending) order, as TokOut records cand[row * kTopkMax + j]; j = 0 repeats the record
@@ -324,7 +327,7 @@ size_t logits_rec_bytes(int n_seq);
 // a record j > 0 without a token has id = -1. Rows are t = 0 rows (want_probs is ignored).
 constexpr int kTopkMax = 8;
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
-                        void* rec, hipStream_t st);
+                        void* rec, const uint32_t* deny, hipStream_t st);
 // ---- sampled draw (kernels/sample.hip; best_of candidates of a t > 0 attempt) -------
 // Row r < n (<= kSampleMaxRows, one workgroup each) draws a token from probs row src = ctr[r][3] of the
 // [.][2][n_vocab] buffer launch_logits fills for want_probs rows: uniform word x0 = words[r] if words, else

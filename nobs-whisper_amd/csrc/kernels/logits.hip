@@ -4,7 +4,8 @@
 // from L2 and returns only a TokOut record (token id, p, plog, tid, pt, ptsum, no-speech prob),
 // so the host never copies a [B, V] logits block per step. Rules, in whisper.cpp's order [ext]:
 // temperature divide; suppress_blank (initial step: EOT and " "); <|notimestamps|>; optional
-// no_timestamps; sot/nosp/solm/translate/transcribe/prev; the 100 language tokens; timestamp
+// no_timestamps; sot/nosp/solm/translate/transcribe/prev; the 100 language tokens; the deny mask of
+// suppress_nst / suppress_regex (masked_deny; only when the call has one); timestamp
 // pairing; max_initial_ts; monotonic timestamps; log-softmax; "sum(p(timestamps)) > max p(text)
 // => timestamp"; probs = exp(logprob). Greedy argmax keeps whisper's first-index tie break over
 // the float probs. When temperature > 0 the probs row is also written for host-side sampling
@@ -38,6 +39,18 @@ __device__ __forceinline__ float masked_logit(float x, int i, const SeqCtl& c, c
     if (c.is_initial && c.tid0_initial >= 0 && i >= v.beg + c.tid0_initial + 1) return -INFINITY;
     if (c.has_ts && i >= v.beg && i < v.beg + c.seek_delta / 2) return -INFINITY;
     return x;
+}
+
+// DM: the deny mask of suppress_nst / suppress_regex: bit i & 31 of word i >> 5 set = token i is
+// denied, whatever the other rules say. 0: no mask (deny is not read: the code of a launch without one is what it
+// was before the mask existed), 1: deny is the device buffer, read through the cache, 2: deny is the workgroup's
+// copy in LDS. i < n_vocab.
+template <int DM>
+__device__ __forceinline__ float masked_deny(float x, int i, const SeqCtl& c, const VocabIds& v, const uint32_t* deny) {
+    if constexpr (DM != 0) {
+        if ((deny[i >> 5] >> (i & 31)) & 1u) return -INFINITY;
+    }
+    return masked_logit(x, i, c, v);
 }
 
 __device__ float block_max(float x, float* sh) {
@@ -109,8 +122,54 @@ struct RowSlice {
     }
 };
 
+// The deny mask in the 1024-thread kernels: the device words (DM 1), or DM 2: the workgroup's copy behind the row's
+// LDS part. load() issues the copy's loads (before the row's, so they are in flight together), store() writes them to
+// LDS and is followed by the caller's barrier. A thread owns ids tid + 1024 k: bit tid & 31 of the words
+// (tid >> 5) + 32 k, so a wave reads two words per k (from LDS one broadcast read) and the test is one AND.
+template <int DM>
+struct DenyLane {
+    static constexpr int NW = (NPT * LT / 32 + LT - 1) / LT;  // words per thread of the copy
+    const uint32_t* words = nullptr;                          // what masked_deny reads
+    const uint32_t* lane = nullptr;
+    uint32_t bit = 0, stage[NW];
+    __device__ __forceinline__ void load(const uint32_t* __restrict__ deny, float* s_row, int n) {
+        if constexpr (DM == 0) return;
+        words = deny;
+        if constexpr (DM == 2) {
+            words = (const uint32_t*)(s_row + NPT_LDS * LT);
+#pragma unroll
+            for (int j = 0; j < NW; j++) {
+                const int w = threadIdx.x + j * LT;
+                stage[j] = w < (n + 31) >> 5 ? deny[w] : 0u;
+            }
+        }
+        lane = words + (threadIdx.x >> 5);
+        bit = 1u << (threadIdx.x & 31);
+    }
+    __device__ __forceinline__ void store(float* s_row, int n) {
+        if constexpr (DM == 2) {
+            uint32_t* sd = (uint32_t*)(s_row + NPT_LDS * LT);
+#pragma unroll
+            for (int j = 0; j < NW; j++) {
+                const int w = threadIdx.x + j * LT;
+                if (w < (n + 31) >> 5) sd[w] = stage[j];
+            }
+        }
+    }
+    // id threadIdx.x + k * LT (< n_vocab) is denied
+    __device__ __forceinline__ bool denied(int k) const {
+        if constexpr (DM == 0) return false;
+        else return (lane[k * (LT / 32)] & bit) != 0;
+    }
+};
+static size_t row_lds_bytes(int dm, int n_vocab) {
+    return (size_t)NPT_LDS * LT * sizeof(float) + (dm == 2 ? (size_t)((n_vocab + 31) / 32) * sizeof(uint32_t) : 0);
+}
+
+template <int DM>
 __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
-                                                    VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs) {
+                                                    VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs,
+                                                    const uint32_t* __restrict__ deny) {
     const int s = blockIdx.x;
     const SeqCtl c = ctl[s];
     const float* L = logits + (long)s * ld;
@@ -121,6 +180,9 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
 
     extern __shared__ float s_row[];  // [NPT_LDS][LT]
     RowSlice x{s_row};
+    DenyLane<DM> dl;
+    dl.load(deny, s_row, n);
+    const uint32_t* dm = dl.words;
     // the register part first, then the LDS part in batches of 12 loads in flight (a load -> LDS
     // store pair per element would wait out one memory latency per element)
 #pragma unroll
@@ -155,10 +217,12 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         nosp_prob = expf(L[v.nosp] - lse);
     }
     // filtered logits, in place
+    dl.store(s_row, n);
+    if constexpr (DM == 2) __syncthreads();  // the mask's LDS copy
 #pragma unroll
     for (int k = 0; k < NPT; k++) {
         const int i = tid + k * LT;
-        if (i < n) x.set(k, masked_logit(x.get(k), i, c, v));
+        if (i < n) x.set(k, dl.denied(k) ? -INFINITY : masked_logit(x.get(k), i, c, v));
     }
     // log-softmax of the filtered logits
     float mx = -INFINITY;
@@ -221,7 +285,7 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         r.id = best > 0.0f ? ibest : 0;
         r.p = best;
         {
-            float xv = masked_logit(L[r.id], r.id, c, v);
+            float xv = masked_deny<DM>(L[r.id], r.id, c, v, dm);
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
         }
@@ -241,8 +305,10 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
 // tokens with p > 0 in (p descending, id ascending) order. A text candidate carries the row's tid / pt / ptsum, a
 // timestamp candidate tid = id and pt = p (as the greedy record does); when fewer than topk tokens have p > 0
 // the remaining records have id = -1. (A copy, not a template flag: the greedy kernel's code stays as it was.)
+template <int DM>
 __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
-                                                         VocabIds v, TokOut* __restrict__ out, int topk) {
+                                                         VocabIds v, TokOut* __restrict__ out, int topk,
+                                                         const uint32_t* __restrict__ deny) {
     const int s = blockIdx.x;
     const SeqCtl c = ctl[s];
     const float* L = logits + (long)s * ld;
@@ -254,6 +320,9 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
 
     extern __shared__ float s_row[];  // [NPT_LDS][LT]
     RowSlice x{s_row};
+    DenyLane<DM> dl;
+    dl.load(deny, s_row, n);
+    const uint32_t* dm = dl.words;
     // the register part first, then the LDS part in batches of 12 loads in flight (a load -> LDS
     // store pair per element would wait out one memory latency per element)
 #pragma unroll
@@ -288,10 +357,12 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
         nosp_prob = expf(L[v.nosp] - lse);
     }
     // filtered logits, in place
+    dl.store(s_row, n);
+    if constexpr (DM == 2) __syncthreads();  // the mask's LDS copy
 #pragma unroll
     for (int k = 0; k < NPT; k++) {
         const int i = tid + k * LT;
-        if (i < n) x.set(k, masked_logit(x.get(k), i, c, v));
+        if (i < n) x.set(k, dl.denied(k) ? -INFINITY : masked_logit(x.get(k), i, c, v));
     }
     // log-softmax of the filtered logits
     float mx = -INFINITY;
@@ -350,7 +421,7 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
         r.id = best > 0.0f ? ibest : 0;
         r.p = best;
         {
-            float xv = masked_logit(L[r.id], r.id, c, v);
+            float xv = masked_deny<DM>(L[r.id], r.id, c, v, dm);
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
         }
@@ -390,7 +461,7 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
             } else {
                 r.id = ij;
                 r.p = bj;
-                r.plog = masked_logit(L[ij], ij, c, v) - lse;  // p > 0: the filtered logit is finite
+                r.plog = masked_deny<DM>(L[ij], ij, c, v, dm) - lse;  // p > 0: the filtered logit is finite
                 if (ij >= v.beg) { r.tid = ij; r.pt = bj; }
                 else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
             }
@@ -455,9 +526,12 @@ __device__ void blk_argmax(float& v, int& ix, float* shv, int* shi) {
     for (int i = 1; i < NW; i++) argmax_pair(v, ix, shv[i], shi[i]);
 }
 
+// (DM 0 / 1 in the split form's 256-thread kernels: a chunk workgroup needs ~102 words of the mask once each, so
+// they come through the cache)
+template <int DM>
 __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restrict__ logits, long ld,
                                                           const SeqCtl* __restrict__ ctl, VocabIds v,
-                                                          LogitRec* __restrict__ rec) {
+                                                          LogitRec* __restrict__ rec, const uint32_t* __restrict__ dm) {
     constexpr int NW = LT2 / 64, PER = 14;  // 14 * 256 * 16 >= 51866
     const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
@@ -470,6 +544,14 @@ __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restric
     for (int k = 0; k < PER; k++) {
         const int i = i0 + tid + k * LT2;
         raw[k] = i < i1 ? L[i] : -INFINITY;
+    }
+    uint32_t dw[DM ? PER : 1];  // the mask's words of this thread's ids, in flight with the row
+    if constexpr (DM != 0) {
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int i = i0 + tid + k * LT2;
+            dw[k] = i < i1 ? dm[i >> 5] : 0u;
+        }
     }
     LogitRec r;
     r.m_r = -INFINITY; r.s_r = 0.0f; r.pad = 0;
@@ -490,7 +572,9 @@ __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         const int i = i0 + tid + k * LT2;
-        const float x = i < i1 ? masked_logit(raw[k], i, q, v) : -INFINITY;
+        bool denied = false;
+        if constexpr (DM != 0) denied = (dw[k] >> (i & 31)) & 1u;
+        const float x = i < i1 && !denied ? masked_logit(raw[k], i, q, v) : -INFINITY;
         raw[k] = x;
         if (x > -INFINITY) {
             argmax_pair(m, ix, x, i);
@@ -516,10 +600,11 @@ __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restric
     if (tid == 0) rec[(long)s * KS + c] = r;
 }
 
+template <int DM>
 __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __restrict__ logits, long ld,
                                                              const SeqCtl* __restrict__ ctl, VocabIds v,
                                                              const LogitRec* __restrict__ rec, TokOut* __restrict__ out,
-                                                             float* __restrict__ probs) {
+                                                             float* __restrict__ probs, const uint32_t* __restrict__ dm) {
     const int s = blockIdx.x, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
     const float* L = logits + (long)s * ld;
@@ -552,7 +637,7 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
         r.id = best > 0.0f ? ib : 0;
         r.p = best;
         {
-            float xv = masked_logit(L[r.id], r.id, q, v);
+            float xv = masked_deny<DM>(L[r.id], r.id, q, v, dm);
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
         }
@@ -573,7 +658,7 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
     const float lse = sh_lse;
     const bool mask_text = sh_mask;
     for (int i = tid; i < n; i += LT2) {
-        float xv = masked_logit(L[i], i, q, v);
+        float xv = masked_deny<DM>(L[i], i, q, v, dm);
         if (mask_text && i < v.beg) xv = -INFINITY;
         probs[(long)s * 2 * n + i] = xv == -INFINITY ? 0.0f : __expf(xv - lse);
         probs[(long)s * 2 * n + n + i] = xv == -INFINITY ? -INFINITY : xv - lse;
@@ -587,10 +672,11 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
 // timestamp rule fired) without the earlier winners, with p = e^(x - lse), plog = x - lse: the split form's own
 // key (it orders by x where the one-workgroup form orders by the rounded p). A candidate whose p underflows
 // to 0, and every one after it, has id = -1.
+template <int DM>
 __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __restrict__ logits, long ld,
                                                                  const SeqCtl* __restrict__ ctl, VocabIds v,
                                                                  const LogitRec* __restrict__ rec, TokOut* __restrict__ cand,
-                                                                 int topk) {
+                                                                 int topk, const uint32_t* __restrict__ deny) {
     const int s = blockIdx.x, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
     const float* L = logits + (long)s * ld;
@@ -602,10 +688,15 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
     __shared__ int sh_win;       // the last winner (-1: no token with p > 0 is left)
     extern __shared__ float s_row[];  // [NPT_LDS][LT]
     RowSlice x{s_row};
+    DenyLane<DM> dl;
+    dl.load(deny, s_row, n);
+    dl.store(s_row, n);
+    const uint32_t* dm = dl.words;
+    if constexpr (DM == 2) __syncthreads();  // the mask's LDS copy
 #pragma unroll
     for (int k = NPT_LDS; k < NPT; k++) {
         const int i = tid + k * LT;
-        x.set(k, i < n ? masked_logit(L[i], i, q, v) : -INFINITY);
+        x.set(k, i < n ? (dl.denied(k) ? -INFINITY : masked_logit(L[i], i, q, v)) : -INFINITY);
     }
 #pragma unroll
     for (int k0 = 0; k0 < NPT_LDS; k0 += 12) {
@@ -618,7 +709,7 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
 #pragma unroll
         for (int k = 0; k < 12; k++) {
             const int i = tid + (k0 + k) * LT;
-            x.set(k0 + k, i < n ? masked_logit(t[k], i, q, v) : -INFINITY);
+            x.set(k0 + k, i < n ? (dl.denied(k0 + k) ? -INFINITY : masked_logit(t[k], i, q, v)) : -INFINITY);
         }
     }
     if (tid == 0) {
@@ -648,7 +739,7 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
         r.id = best > 0.0f ? ib : 0;
         r.p = best;
         {
-            float xv = masked_logit(L[r.id], r.id, q, v);
+            float xv = masked_deny<DM>(L[r.id], r.id, q, v, dm);
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
         }
@@ -707,32 +798,56 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
 // rows up to this count take the split form (16 chunk workgroups per row + a combine)
 static const int kLogitsSplitMax = 16;
 
+// the form the 1024-thread kernels read a mask in: 2 (LDS), or 1 (through the cache) under
+// WHISPER_MI355X_DENY_GLOBAL=1 (the measurement of DESIGN.md §15; read per launch, a captured step keeps its form)
+static int deny_mode(const uint32_t* deny) {
+    if (!deny) return 0;
+    const char* e = getenv("WHISPER_MI355X_DENY_GLOBAL");
+    return e && atoi(e) > 0 ? 1 : 2;
+}
+
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* out, float* probs,
-                   void* rec, hipStream_t st) {
+                   void* rec, const uint32_t* deny, hipStream_t st) {
     if (n_seq <= 0) return;
     if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
     if (rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
-        logits_part_kernel<<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec);
-        logits_combine_kernel<<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs);
+        if (deny) {
+            logits_part_kernel<1><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny);
+            logits_combine_kernel<1><<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs, deny);
+        } else {
+            logits_part_kernel<0><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, nullptr);
+            logits_combine_kernel<0><<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs, nullptr);
+        }
         return;
     }
-    logits_kernel<<<n_seq, LT, (size_t)NPT_LDS * LT * sizeof(float), st>>>(logits, ld, ctl, v, out, probs);
+    const int dm = deny_mode(deny);
+    const size_t lds = row_lds_bytes(dm, v.n_vocab);
+    if (dm == 2) logits_kernel<2><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, deny);
+    else if (dm == 1) logits_kernel<1><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, deny);
+    else logits_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, nullptr);
 }
 
 // Top-k after the rules: the form is chosen exactly as launch_logits chooses it for the same n_seq / rec, so
 // candidate 0 of a row is the TokOut launch_logits would return for it.
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
-                        void* rec, hipStream_t st) {
+                        void* rec, const uint32_t* deny, hipStream_t st) {
     if (n_seq <= 0) return;
     if (k < 1 || k > kTopkMax) WM_FAIL("top-k %d outside 1..%d", k, kTopkMax);
     if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
-    const size_t lds = (size_t)NPT_LDS * LT * sizeof(float);
+    const int dm = deny_mode(deny);
+    const size_t lds = row_lds_bytes(dm, v.n_vocab);
     if (rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
-        logits_part_kernel<<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec);
-        logits_topk_combine_kernel<<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, cand, k);
+        const LogitRec* R = (const LogitRec*)rec;
+        if (deny) logits_part_kernel<1><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny);
+        else logits_part_kernel<0><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, nullptr);
+        if (dm == 2) logits_topk_combine_kernel<2><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny);
+        else if (dm == 1) logits_topk_combine_kernel<1><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny);
+        else logits_topk_combine_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, nullptr);
         return;
     }
-    logits_topk_kernel<<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k);
+    if (dm == 2) logits_topk_kernel<2><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, deny);
+    else if (dm == 1) logits_topk_kernel<1><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, deny);
+    else logits_topk_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, nullptr);
 }
 
 // ---- device-side step advance (pipelined greedy decoding, engine.cpp decode_pipelined) -----------------------

@@ -187,6 +187,12 @@ def lib() -> C.CDLL:
                                                        C.POINTER(Cand)]),
         "whisper_mi355x_debug_kv_gather": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, ip]),
         "whisper_mi355x_debug_logits": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, C.POINTER(Cand), fp]),
+        "whisper_mi355x_suppress_mask": (C.c_int, [vp, C.c_bool, C.c_char_p, C.POINTER(C.c_uint32), C.c_int]),
+        "whisper_mi355x_suppress_builds": (C.c_long, [vp]),
+        "whisper_mi355x_debug_logits_deny": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, C.POINTER(Cand), fp,
+                                                       C.POINTER(C.c_uint32)]),
+        "whisper_mi355x_debug_logits_topk_deny": (C.c_int, [vp, vp, C.c_int, ip, fp, C.c_int, C.c_int, C.POINTER(Cand),
+                                                            C.POINTER(Cand), C.POINTER(C.c_uint32)]),
         "whisper_mi355x_debug_decode_advance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Cand), ip,
                                                           C.POINTER(SeqCtl), C.POINTER(C.c_uint), C.POINTER(Cand),
                                                           C.POINTER(C.c_uint)]),
@@ -344,6 +350,21 @@ class WhisperContext:
     def token_str(self, token: int) -> bytes:
         """whisper_token_to_str: the token's bytes (specials included)."""
         return self.L.whisper_token_to_str(self.ptr, token) or b""
+
+    def suppress_mask(self, suppress_nst: bool = False, regex: str | None = None):
+        """whisper_mi355x_suppress_mask: the deny mask of FullParams.suppress_nst / suppress_regex for this vocabulary as
+        a bool array [n_vocab] (host only), or the negative return code (-8: the pattern does not compile)."""
+        import numpy as np
+        V = self.L.whisper_n_vocab(self.ptr)
+        w = np.zeros((V + 31) // 32, np.uint32)
+        rc = self.L.whisper_mi355x_suppress_mask(self.ptr, suppress_nst, None if regex is None else regex.encode(),
+                                                 w.ctypes.data_as(C.POINTER(C.c_uint32)), len(w))
+        if rc < 0:
+            return rc
+        assert rc == len(w)
+        bits = np.unpackbits(w.view(np.uint8), bitorder="little")
+        assert not bits[V:].any(), "bits at and above n_vocab"
+        return bits[:V].astype(bool)
 
     @staticmethod
     def clip_offsets(n_samples) -> list:
