@@ -42,7 +42,15 @@
  * off), get a logit of -inf in every decoding mode. A pattern that does not compile makes whisper_full* return -8
  * before anything is encoded, with one line on stderr (upstream throws std::regex_error).
  *
- * Still accepted and ignored: the grammar fields, tdrz_enable and vad (with vad_model_path and vad_params).
+ * whisper_full_params.grammar_rules, n_grammar_rules, i_start_rule and grammar_penalty are implemented (DESIGN.md §16,
+ * whisper_mi355x.h) with upstream's semantics in every decoding mode: each decoder, beam and best_of candidate follows the
+ * grammar from its start state, and every token the grammar rejects loses grammar_penalty before the token is chosen
+ * (EOT too, unless the grammar may end there). n_grammar_rules == 0 or grammar_rules == NULL: no grammar. A malformed
+ * grammar (a null rule, i_start_rule >= n_grammar_rules, a RULE_REF out of range, a CHAR_RNG_UPPER or CHAR_ALT that does
+ * not follow a char class) or a left-recursive one (upstream recurses without end) makes whisper_full* return -9 before
+ * anything is encoded, with one line on stderr.
+ *
+ * Still accepted and ignored: tdrz_enable and vad (with vad_model_path and vad_params).
  */
 #ifndef WHISPER_H
 #define WHISPER_H

@@ -415,6 +415,49 @@ WHISPER_API int whisper_mi355x_debug_logits_topk_deny(struct whisper_context * c
                                                       struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy,
                                                       const uint32_t * deny);
 
+/* whisper_full_params.grammar_rules, n_grammar_rules, i_start_rule and grammar_penalty (whisper.h).
+ * A decoder keeps a grammar state (a list of stacks of rule positions and a pending partial UTF-8 character), advanced by
+ * every token that is fed next; before each logits step the state's reject mask over the vocabulary is taken, and the
+ * logits kernels subtract grammar_penalty from every rejected token (and from EOT unless the grammar may end here), after
+ * the timestamp rule and only when that rule did not mask the text tokens, and take the row's log-softmax again.
+ * whisper_mi355x_grammar_mask: the reject mask of the state that init and the accepted tokens reach, for this context's
+ * vocabulary, as whisper_full* builds it. Host only. words (cap_words >= (n_vocab + 31) / 32): token i is bit i & 31 of
+ * word i >> 5; set = a token below EOT with a non-empty string that the state rejects; the EOT bit = the grammar may not
+ * end here; bits above EOT are 0; a state whose stack list is empty (the grammar was violated: it is off for the rest of
+ * the attempt) gives all zeros. Returns the word count, -1 on bad arguments, -9 when the grammar is refused (a null
+ * rule, i_start >= n_rules, a RULE_REF out of range, a CHAR_RNG_UPPER or CHAR_ALT that does not follow a char class,
+ * more than 65535 elements, left recursion; one stderr line). */
+WHISPER_API int whisper_mi355x_grammar_mask(struct whisper_context * ctx, const whisper_grammar_element ** rules,
+                                            size_t n_rules, size_t i_start, const whisper_token * accepted_tokens,
+                                            int n_accepted, uint32_t * words, int cap_words);
+/* Rows of grammar calls on this state (and on the second state a batch of more than 128 clips runs its other half on)
+ * since it was created or recycled: rows whose mask the reject kernel (kernels/grammar.hip) decided, rows it flagged (a
+ * token's simulation exceeded the kernel's bounds) and the host patched, rows the host built because the kernel does not
+ * take their state (more than 32 stacks, a stack deeper than 16, a pending partial UTF-8 character); and the reject
+ * kernel's time and launches from the kernel-timing class 16 (K_GRAMMAR; whisper_mi355x_kernel_timing with bit 16 set,
+ * else 0). */
+struct whisper_mi355x_grammar_stats { long rows_device, rows_patched, rows_host; double kernel_ms; long kernel_launches; };
+WHISPER_API int whisper_mi355x_grammar_stats(struct whisper_state * state, struct whisper_mi355x_grammar_stats * out);
+/* Debug: the reject masks of n_rows grammar states through the device path of whisper_full*, fallback included. Row r's
+ * state is init plus accept of its n_accepted[r] tokens, which follow one another in accepted_tokens. words
+ * [n_rows][(n_vocab + 31) / 32] receives the masks as read back from the device; flags[r]: 0 decided by the kernel,
+ * 1 patched by the host after the kernel flagged the row, 2 built by the host alone. Returns the word count per row, -1
+ * on bad arguments (no rules included), -9 for a refused grammar. */
+WHISPER_API int whisper_mi355x_debug_grammar_reject(struct whisper_context * ctx, const whisper_grammar_element ** rules,
+                                                    size_t n_rules, size_t i_start, const whisper_token * accepted_tokens,
+                                                    const int * n_accepted, int n_rows, uint32_t * words, int * flags);
+/* Debug: the _deny hooks with the grammar's reject words: gram = host [n][(n_vocab + 31) / 32] words, row r's mask as
+ * above, uploaded and given to the launches with `penalty` (the launches then take the one-workgroup-per-row form,
+ * whatever form / split say), or NULL: the _deny hooks, bit for bit. */
+WHISPER_API int whisper_mi355x_debug_logits_gram(struct whisper_context * ctx, const float * logits, int n,
+                                                 const struct whisper_mi355x_seq_ctl * ctl, int form,
+                                                 struct whisper_mi355x_cand * out, float * probs, const uint32_t * deny,
+                                                 const uint32_t * gram, float penalty);
+WHISPER_API int whisper_mi355x_debug_logits_topk_gram(struct whisper_context * ctx, const float * logits, int n,
+                                                      const int * rules, const float * temperature, int k, int split,
+                                                      struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy,
+                                                      const uint32_t * deny, const uint32_t * gram, float penalty);
+
 /* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
  * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.
  * scores: q [n_text_layer][sum n_rows][d] (device, compute type: the cross-Q rows of every layer, already scaled

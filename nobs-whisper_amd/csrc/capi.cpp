@@ -918,6 +918,14 @@ static const uint32_t* hook_deny(HookBufs& b, const uint32_t* deny, int n_vocab,
     WM_CHECK(hipMemcpyAsync(d, deny, bytes, hipMemcpyHostToDevice, st));
     return d;
 }
+// the grammar words of a hook's n rows on the device (null stays null: the launch without a grammar)
+static const uint32_t* hook_gram(HookBufs& b, const uint32_t* gram, int n, int n_vocab, hipStream_t st) {
+    if (!gram) return nullptr;
+    const size_t bytes = (size_t)n * grammar_words(n_vocab) * sizeof(uint32_t);
+    uint32_t* d = (uint32_t*)b.get(bytes);
+    WM_CHECK(hipMemcpyAsync(d, gram, bytes, hipMemcpyHostToDevice, st));
+    return d;
+}
 int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* logits, int n, const int* rules,
                                      const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,
                                      struct whisper_mi355x_cand* greedy) {
@@ -926,6 +934,12 @@ int whisper_mi355x_debug_logits_topk(struct whisper_context* ctx, const float* l
 int whisper_mi355x_debug_logits_topk_deny(struct whisper_context* ctx, const float* logits, int n, const int* rules,
                                           const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,
                                           struct whisper_mi355x_cand* greedy, const uint32_t* deny) {
+    return whisper_mi355x_debug_logits_topk_gram(ctx, logits, n, rules, temperature, k, split, cand, greedy, deny, nullptr, 0.0f);
+}
+int whisper_mi355x_debug_logits_topk_gram(struct whisper_context* ctx, const float* logits, int n, const int* rules,
+                                          const float* temperature, int k, int split, struct whisper_mi355x_cand* cand,
+                                          struct whisper_mi355x_cand* greedy, const uint32_t* deny, const uint32_t* gram,
+                                          float penalty) {
     return guarded(nullptr, [&]() -> int {
         if (!ctx || !logits || !rules || !cand || !greedy || n <= 0 || k < 1 || k > kTopkMax) return -1;
         hipSetDevice(ctx->c.device);
@@ -943,8 +957,9 @@ int whisper_mi355x_debug_logits_topk_deny(struct whisper_context* ctx, const flo
         void* rec = split ? b.get(logits_rec_bytes(n)) : nullptr;
         WM_CHECK(hipMemcpyAsync(d_ctl, ctl.data(), n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
         const uint32_t* d_deny = hook_deny(b, deny, V, st);
-        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out + (size_t)n * kTopkMax, nullptr, rec, d_deny, st);
-        launch_logits_topk(logits, V, d_ctl, n, ctx->c.vid, d_out, k, rec, d_deny, st);
+        const uint32_t* d_gram = hook_gram(b, gram, n, V, st);
+        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out + (size_t)n * kTopkMax, nullptr, rec, d_deny, d_gram, penalty, st);
+        launch_logits_topk(logits, V, d_ctl, n, ctx->c.vid, d_out, k, rec, d_deny, d_gram, penalty, st);
         std::vector<TokOut> out((size_t)n * (kTopkMax + 1));
         WM_CHECK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         WM_CHECK(hipStreamSynchronize(st));
@@ -1077,6 +1092,83 @@ long whisper_mi355x_suppress_builds(struct whisper_context* ctx) {
     std::lock_guard<std::mutex> lk(ctx->c.deny_mu);
     return ctx->c.deny_builds;
 }
+// ---- whisper_full_params.grammar_rules (grammar.h; host only) ----------------------------------------------------------
+int whisper_mi355x_grammar_mask(struct whisper_context* ctx, const whisper_grammar_element** rules, size_t n_rules,
+                                size_t i_start, const whisper_token* accepted_tokens, int n_accepted, uint32_t* words,
+                                int cap_words) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !words || n_accepted < 0 || (n_accepted > 0 && !accepted_tokens) ||
+            cap_words < grammar_words(ctx->c.hp.n_vocab))
+            return -1;
+        whisper_full_params p{};
+        p.grammar_rules = rules;
+        p.n_grammar_rules = n_rules;
+        p.i_start_rule = i_start;
+        GrammarRules g;
+        if (const int r = grammar_check(p, g)) return r;
+        Grammar st;
+        st.init(g);
+        const Vocab& v = ctx->c.vocab;
+        for (int k = 0; k < n_accepted; k++) {
+            if (accepted_tokens[k] < 0 || accepted_tokens[k] >= (int)v.id_to_token.size()) return -1;
+            st.accept_token(g, v.id_to_token[accepted_tokens[k]]);
+        }
+        grammar_reject(g, gram_vocab(&ctx->c), st, words);
+        return grammar_words(ctx->c.hp.n_vocab);
+    });
+}
+int whisper_mi355x_grammar_stats(struct whisper_state* state, struct whisper_mi355x_grammar_stats* out) {
+    if (!state || !out) return -1;
+    memset(out, 0, sizeof(*out));
+    for (const whisper_state* s : {(const whisper_state*)state, (const whisper_state*)state->twin}) {  // (a paired batch's second half)
+        if (!s) continue;
+        out->rows_device += s->ws.gd.rows_device;
+        out->rows_patched += s->ws.gd.rows_patched;
+        out->rows_host += s->ws.gd.rows_host;
+        out->kernel_ms += s->kstat[K_GRAMMAR].ms;
+        out->kernel_launches += s->kstat[K_GRAMMAR].count;
+    }
+    return 0;
+}
+int whisper_mi355x_debug_grammar_reject(struct whisper_context* ctx, const whisper_grammar_element** rules, size_t n_rules,
+                                        size_t i_start, const whisper_token* accepted_tokens, const int* n_accepted, int n_rows,
+                                        uint32_t* words, int* flags) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !n_accepted || !words || !flags || n_rows <= 0) return -1;
+        whisper_full_params p{};
+        p.grammar_rules = rules;
+        p.n_grammar_rules = n_rules;
+        p.i_start_rule = i_start;
+        GrammarRules g;
+        if (const int r = grammar_check(p, g)) return r;
+        if (!g.on()) return -1;
+        const Vocab& v = ctx->c.vocab;
+        std::vector<Grammar> states(n_rows);
+        std::vector<const Grammar*> ptrs(n_rows);
+        size_t k = 0;
+        for (int r = 0; r < n_rows; r++) {
+            if (n_accepted[r] < 0 || (n_accepted[r] > 0 && !accepted_tokens)) return -1;
+            states[r].init(g);
+            for (int i = 0; i < n_accepted[r]; i++, k++) {
+                if (accepted_tokens[k] < 0 || accepted_tokens[k] >= (int)v.id_to_token.size()) return -1;
+                states[r].accept_token(g, v.id_to_token[accepted_tokens[k]]);
+            }
+            ptrs[r] = &states[r];
+        }
+        hipSetDevice(ctx->c.device);
+        const size_t W = grammar_words(ctx->c.hp.n_vocab), bytes = (size_t)n_rows * W * sizeof(uint32_t);
+        HookBufs b;
+        HookStream hs;
+        struct Dev { GramDev d; ~Dev() { gram_dev_free(d); } } dev;
+        uint32_t* d_gram = (uint32_t*)b.get(bytes);
+        WM_CHECK(hipMemsetAsync(d_gram, 0xff, bytes, hs.st));  // (words nothing writes would show)
+        gram_dev_rules(dev.d, g, hs.st);
+        gram_masks(&ctx->c, dev.d, g, ptrs.data(), n_rows, d_gram, words, flags, hs.st, nullptr);  // (words: the staging too)
+        WM_CHECK(hipMemcpyAsync(words, d_gram, bytes, hipMemcpyDeviceToHost, hs.st));
+        WM_CHECK(hipStreamSynchronize(hs.st));
+        return (int)W;
+    });
+}
 // ---- the greedy logits kernels and the step advance on caller data (kernels/logits.hip) --------------------------
 static_assert(sizeof(whisper_mi355x_seq_ctl) == sizeof(SeqCtl), "whisper_mi355x_seq_ctl mirrors SeqCtl");
 int whisper_mi355x_debug_logits(struct whisper_context* ctx, const float* logits, int n,
@@ -1087,6 +1179,11 @@ int whisper_mi355x_debug_logits(struct whisper_context* ctx, const float* logits
 int whisper_mi355x_debug_logits_deny(struct whisper_context* ctx, const float* logits, int n,
                                      const struct whisper_mi355x_seq_ctl* ctl, int form, struct whisper_mi355x_cand* out,
                                      float* probs, const uint32_t* deny) {
+    return whisper_mi355x_debug_logits_gram(ctx, logits, n, ctl, form, out, probs, deny, nullptr, 0.0f);
+}
+int whisper_mi355x_debug_logits_gram(struct whisper_context* ctx, const float* logits, int n,
+                                     const struct whisper_mi355x_seq_ctl* ctl, int form, struct whisper_mi355x_cand* out,
+                                     float* probs, const uint32_t* deny, const uint32_t* gram, float penalty) {
     return guarded(nullptr, [&]() -> int {
         if (!ctx || !logits || !ctl || !out || n <= 0 || form < 0 || form > 1) return -1;
         for (int r = 0; r < n; r++)
@@ -1103,7 +1200,8 @@ int whisper_mi355x_debug_logits_deny(struct whisper_context* ctx, const float* l
         void* rec = form ? b.get(logits_rec_bytes(n)) : nullptr;
         WM_CHECK(hipMemcpyAsync(d_ctl, ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
         if (d_probs) WM_CHECK(hipMemsetAsync(d_probs, 0xff, pbytes, st));  // rows the kernel leaves alone read as NaN
-        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out, d_probs, rec, hook_deny(b, deny, V, st), st);
+        const uint32_t* d_deny = hook_deny(b, deny, V, st);
+        launch_logits(logits, V, d_ctl, n, ctx->c.vid, d_out, d_probs, rec, d_deny, hook_gram(b, gram, n, V, st), penalty, st);
         WM_CHECK(hipGetLastError());
         WM_CHECK(hipMemcpyAsync(out, d_out, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         if (d_probs) WM_CHECK(hipMemcpyAsync(probs, d_probs, pbytes, hipMemcpyDeviceToHost, st));

@@ -192,6 +192,9 @@ static void reset_for_reuse(whisper_state* s) {
     s->pdec_off = false;
     s->mode = StepMode{};
     s->deny_on = false;
+    s->gram_on = false;
+    s->ws.gd.host_masks.clear();
+    s->ws.gd.rows_device = s->ws.gd.rows_patched = s->ws.gd.rows_host = 0;
     s->beam_info.clear();
     s->sample_seed = 0;
     s->cand_info.clear();
@@ -319,7 +322,9 @@ static void free_ws(Workspace& w) {
     dfree(w.pcm); dfree(w.mel); dfree(w.mel_ptrs); dfree(w.splitk); dfree(w.enc); dfree(w.qx); dfree(w.xo);
     dfree(w.xml); dfree(w.kvslot); dfree(w.hs); dfree(w.qtiles); dfree(w.wdq); dfree(w.pd_sync);
     dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage); dfree(w.sctr);
-    dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans); dfree(w.deny);
+    dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans); dfree(w.deny); dfree(w.gram);
+    if (w.h_gram) hipHostFree(w.h_gram);
+    gram_dev_free(w.gd);
     if (w.h_sslot) hipHostFree(w.h_sslot);
     if (w.h_sctr) hipHostFree(w.h_sctr);
     if (w.h_cand) hipHostFree(w.h_cand);
@@ -427,9 +432,9 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips
         free_align(w);  // sized by cap_jobs
         for (auto& a : s->align_info) a = {};  // (pointers into al_cost)
         if (w.h_ring) { WM_CHECK(hipHostFree(w.h_ring)); w.h_ring = nullptr; w.ring = nullptr; }
-        dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.sctr);
+        dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.sctr); dfree(w.gram);
         for (void** h : {(void**)&w.h_qtiles, (void**)&w.h_ints, (void**)&w.h_tout, (void**)&w.h_ctl, (void**)&w.h_sslot,
-                         (void**)&w.h_cand, (void**)&w.h_kvcp, (void**)&w.h_sctr})
+                         (void**)&w.h_cand, (void**)&w.h_kvcp, (void**)&w.h_sctr, (void**)&w.h_gram})
             if (*h) { void* q = *h; *h = nullptr; WM_CHECK(hipHostFree(q)); }
         w.cap_jobs = w.cap_tok = w.cap_cross = w.cap_xq = 0;
         // split-K slabs: decode steps (<= 128 rows per group, two concurrent groups) and the prefill
@@ -480,6 +485,8 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips
         WM_CHECK(hipHostMalloc((void**)&w.h_kvcp, (size_t)n_jobs * sizeof(KvCopy), 0));
         dalloc(w.sctr, (size_t)n_jobs * 4 * sizeof(int));
         WM_CHECK(hipHostMalloc((void**)&w.h_sctr, (size_t)n_jobs * 4 * sizeof(int), 0));
+        dalloc(w.gram, (size_t)n_jobs * grammar_words(hp.n_vocab) * sizeof(uint32_t));
+        WM_CHECK(hipHostMalloc((void**)&w.h_gram, (size_t)n_jobs * grammar_words(hp.n_vocab) * sizeof(uint32_t), 0));
         w.cap_jobs = n_jobs;
         w.cap_tok = n_tok;
     }
@@ -1503,6 +1510,10 @@ struct Seq {
     int seek_delta = 100 * WHISPER_CHUNK_SIZE;
     bool has_ts = false, failed = false, completed = false;
     int step = 0;  // index of the last token decoded (advanced by process_step)
+    // the grammar state after `tokens` (a grammar call): set by process_step, which starts every attempt,
+    // beam and candidate from the call's init state with its first token; copied with the sequence when a beam takes
+    // its parent's state
+    Grammar gram;
 };
 
 struct Job {
@@ -1570,6 +1581,10 @@ struct Sched {
     // a callback asked to stop; per row of the last prefill / decode step, a host-sampled row's probs
     bool need_lang = false, ctx_applied = false, aborted = false;
     std::vector<std::vector<float>> probs_rows;
+    // a grammar call: the init state every sequence starts from, and per staged row of the coming logits launch the
+    // grammar state of its sequence (fill_ctl -> ctl_upload)
+    Grammar gram0;
+    std::vector<const Grammar*> gram_rows;
 };
 
 static double now_ms() {
@@ -1626,7 +1641,10 @@ static bool sample_attempt(const Sched& S, const Job& j) {
     return S.sample_n > 1 && j.temp_idx > 0 && S.temps[j.temp_idx] >= 1e-6f;
 }
 
-static void fill_ctl(Sched& S, const Job& j, const Seq& q, SeqCtl& ctl, bool want_nosp) {
+// (r: the row of the staging that ctl is; a grammar call notes the row's grammar state for ctl_upload, which follows the
+// staging at once: the sequences are not touched in between)
+static void fill_ctl(Sched& S, const Job& j, const Seq& q, int r, bool want_nosp) {
+    SeqCtl& ctl = S.s->ws.h_ctl[r];
     const Vocab& v = S.c->vocab;
     const float t = S.temps[j.temp_idx];
     ctl.is_initial = q.tokens.empty();
@@ -1644,6 +1662,10 @@ static void fill_ctl(Sched& S, const Job& j, const Seq& q, SeqCtl& ctl, bool wan
     } else ctl.tid0_initial = -1;
     ctl.want_probs = t >= 1e-6f ? (sample_attempt(S, j) ? 2 : 1) : 0;
     ctl.want_nosp = want_nosp;
+    if (S.s->gram_on) {
+        if ((int)S.gram_rows.size() <= r) S.gram_rows.resize(r + 1, nullptr);
+        S.gram_rows[r] = q.tokens.empty() ? &S.gram0 : &q.gram;
+    }
 }
 
 static void finish_window(Sched& S, Job& j) {
@@ -2068,6 +2090,10 @@ static bool process_step(Sched& S, const Job& j, Seq& q, const TokOut& r, const 
         else { td.tid = r.tid; td.pt = r.pt; }
     }
     if (S.o.forced && S.o.fixed_tokens > 0) td.id = S.o.forced[(long)j.slot * S.o.fixed_tokens + i];
+    if (S.s->gram_on) {  // the grammar follows the token that is fed next (an attempt's first token: from the init state)
+        if (q.tokens.empty()) q.gram = S.gram0;
+        if (td.id >= 0 && td.id < (int)v.id_to_token.size()) q.gram.accept_token(S.s->gram_rules, v.id_to_token[td.id]);
+    }
     q.tokens.push_back(td);
     q.sum_logprobs_all += td.plog;
     S.decoded++;
@@ -2126,9 +2152,21 @@ struct ModeScope {
     ModeScope(const ModeScope&) = delete;
 };
 
+// A grammar call: the reject words of the first n staged rows' grammar states (Sched::gram_rows) into ws.gram, before the
+// rows' logits launch (gram_masks: the reject kernel, the host for what it does not take)
+static void gram_upload(Sched& S, int n) {
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    if ((int)S.gram_rows.size() < n) WM_FAIL("grammar: %d rows to upload, %zu staged", n, S.gram_rows.size());
+    for (int r = 0; r < n; r++)
+        if (!S.gram_rows[r]) WM_FAIL("grammar: row %d of %d was not staged", r, n);
+    gram_masks(S.c, w.gd, s->gram_rules, S.gram_rows.data(), n, w.gram, w.h_gram, nullptr, s->stream, s);
+}
+
 // the SeqCtl of the first n staged rows to the device; true if a row wants its probs
 static bool ctl_upload(Sched& S, int n) {
     Workspace& w = S.s->ws;
+    if (S.s->gram_on) gram_upload(S, n);
     bool any_probs = false;
     for (int r = 0; r < n; r++) any_probs |= w.h_ctl[r].want_probs != 0;
     WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, S.s->stream));
@@ -2137,13 +2175,15 @@ static bool ctl_upload(Sched& S, int n) {
 static void logits_launch(Context* c, whisper_state* s, int n) {
     Workspace& w = s->ws;
     const uint32_t* deny = s->deny_on ? w.deny : nullptr;  // suppress_nst / suppress_regex (deny_prepare)
+    const uint32_t* gram = s->gram_on ? w.gram : nullptr;  // the rows' grammar words (gram_upload)
+    const float pen = s->gram_penalty;
     if (s->mode.topk > 0) {  // a beam step: top-k candidates per row (candidate 0 = the greedy record of the row)
         KT kt(s, K_TOPK, (double)n * c->hp.n_vocab * 4);
-        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->mode.topk, w.lrec, deny, s->stream);
+        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->mode.topk, w.lrec, deny, gram, pen, s->stream);
         return;
     }
     KT kt(s, K_LOGITS, (double)n * c->hp.n_vocab * 4);
-    launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.tout, w.probs, w.lrec, deny, s->stream);
+    launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.tout, w.probs, w.lrec, deny, gram, pen, s->stream);
 }
 static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vector<float>>& probs_rows) {
     Context* c = S.c;
@@ -2170,7 +2210,7 @@ static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vect
 // logits kernel over the prefill rows of the `act` jobs (row r of w.logits belongs to act[r]) + D2H
 static void prefill_logits(Sched& S, const std::vector<int>& act, std::vector<std::vector<float>>& probs_rows) {
     const int n = (int)act.size();
-    for (int r = 0; r < n; r++) fill_ctl(S, S.jobs[act[r]], S.jobs[act[r]].seq, S.s->ws.h_ctl[r], true);
+    for (int r = 0; r < n; r++) fill_ctl(S, S.jobs[act[r]], S.jobs[act[r]].seq, r, true);
     const bool any = ctl_upload(S, n);
     logits_launch(S.c, S.s, n);
     logits_finish(S, n, any, probs_rows);
@@ -2215,12 +2255,15 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     }
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
-            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && g.deny == s->deny_on && (!s->mode.sample || g.seed == s->sample_seed))
+            g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && g.deny == s->deny_on && g.gram == s->gram_on &&
+            (!s->gram_on || g.gram_pen == s->gram_penalty) && (!s->mode.sample || g.seed == s->sample_seed))
             return &g;
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
     g.seed = s->sample_seed;  // (a kernel argument of the draw below)
     g.actx = enc_ctx(c, s);
     g.deny = s->deny_on;
+    g.gram = s->gram_on;
+    g.gram_pen = s->gram_penalty;
     hipGraph_t graph;
     s->capture_ev = &g.ev;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -2347,6 +2390,7 @@ static bool pipe_on() {  // (read per call: tests compare both paths in one proc
 
 static bool pipe_ok(Sched& S, const std::vector<int>& act) {
     if (!pipe_on() || S.o.forced || (S.o.spot_logits && S.o.n_spot > 0)) return false;
+    if (S.s->gram_on) return false;  // the host advances the grammar after every step
     for (size_t k = 0; k < S.jobs.size(); k++) {
         const Job& j = S.jobs[k];
         if (j.phase == PH_DONE) continue;
@@ -2387,7 +2431,7 @@ static void stage_row(Sched& S, const Job& j, const Seq& q, int sslot, int r) {
     stage_token(w, r, q.tokens.back().id, (int)j.prompt.size() + q.step, j.slot);
     w.h_ints[5 * w.cap_tok + r] = r;
     w.h_sslot[r] = sslot;
-    fill_ctl(S, j, q, w.h_ctl[r], false);
+    fill_ctl(S, j, q, r, false);
 }
 
 // the n staged rows to the device (the self slots and the draw counters where the step's mode reads them); true if a
@@ -3174,6 +3218,161 @@ static int deny_prepare(Context* c, whisper_state* s, const whisper_full_params&
     return 0;
 }
 
+// ---- whisper_full_params.grammar_rules (grammar.h) ---------------------------------------------------
+static_assert(sizeof(whisper_grammar_element) == sizeof(GramElem) && offsetof(whisper_grammar_element, value) == offsetof(GramElem, value),
+              "GramElem mirrors whisper_grammar_element");
+int grammar_check(const whisper_full_params& p, GrammarRules& rules) {
+    std::string err;
+    const int r = grammar_compile((const GramElem* const*)p.grammar_rules, p.n_grammar_rules, p.i_start_rule, rules, &err);
+    if (r) fprintf(stderr, "whisper_mi355x: grammar_rules refused: %s\n", err.c_str());
+    return r;
+}
+const GramVocab& gram_vocab(Context* c) {
+    std::lock_guard<std::mutex> lk(c->gram_mu);
+    if (!c->gram_vocab_built) {
+        gram_vocab_build(c->vocab.id_to_token, c->hp.n_vocab, c->vocab.token_eot, c->gram_vocab);
+        c->gram_vocab_built = true;
+    }
+    return c->gram_vocab;
+}
+
+// the vocabulary's table on the device, built with the first grammar call of the context
+static const GramTable& gram_table(Context* c) {
+    const GramVocab& v = gram_vocab(c);
+    std::lock_guard<std::mutex> lk(c->gram_mu);
+    if (!c->gram_tab.off) {
+        std::vector<uint32_t> val(v.eot);
+        std::vector<int> rem(v.eot);
+        for (int i = 0; i < v.eot; i++) {
+            val[i] = v.tail[i].value;
+            rem[i] = i >= (int)v.strs->size() || (*v.strs)[i].empty() ? kGramTokEmpty : v.tail[i].n_remain;
+        }
+        const void* src[4] = {v.off.data(), v.cps.data(), val.data(), rem.data()};
+        const size_t bytes[4] = {v.off.size() * 4, std::max<size_t>(v.cps.size(), 1) * 4, std::max<size_t>(val.size(), 1) * 4,
+                                 std::max<size_t>(rem.size(), 1) * 4};
+        const size_t have[4] = {v.off.size() * 4, v.cps.size() * 4, val.size() * 4, rem.size() * 4};
+        void* mem[4] = {nullptr, nullptr, nullptr, nullptr};  // published when all four are there
+        try {
+            for (int k = 0; k < 4; k++) {
+                WM_CHECK(hipMalloc(&mem[k], bytes[k]));
+                if (have[k]) WM_CHECK(hipMemcpy(mem[k], src[k], have[k], hipMemcpyHostToDevice));
+            }
+        } catch (...) {
+            for (void* q : mem)
+                if (q) hipFree(q);
+            throw;
+        }
+        for (int k = 0; k < 4; k++) c->gram_tab_mem[k] = mem[k];
+        c->gram_tab = GramTable{(const uint32_t*)c->gram_tab_mem[0], (const uint32_t*)c->gram_tab_mem[1],
+                                (const uint32_t*)c->gram_tab_mem[2], (const int*)c->gram_tab_mem[3], v.eot, v.n_vocab};
+    }
+    return c->gram_tab;
+}
+
+void gram_dev_free(GramDev& d) {
+    dfree(d.elems); dfree(d.rule_off); dfree(d.rows); dfree(d.over);
+    if (d.h_rows) hipHostFree(d.h_rows);
+    if (d.h_over) hipHostFree(d.h_over);
+    d = GramDev();
+}
+
+void gram_dev_rules(GramDev& d, const GrammarRules& g, hipStream_t st) {
+    d.host_masks.clear();
+    if (g.elems.size() > d.cap_elems || g.rule_off.size() > d.cap_rules) {
+        WM_CHECK(hipStreamSynchronize(st));  // (a launch of the last call may still read them)
+        dfree(d.elems); dfree(d.rule_off);
+        d.cap_elems = d.cap_rules = 0;
+        dalloc(d.elems, g.elems.size() * sizeof(GramElem));
+        dalloc(d.rule_off, g.rule_off.size() * sizeof(int));
+        d.cap_elems = g.elems.size();
+        d.cap_rules = g.rule_off.size();
+    }
+    WM_CHECK(hipMemcpyAsync(d.elems, g.elems.data(), g.elems.size() * sizeof(GramElem), hipMemcpyHostToDevice, st));
+    WM_CHECK(hipMemcpyAsync(d.rule_off, g.rule_off.data(), g.rule_off.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    WM_CHECK(hipStreamSynchronize(st));  // (the caller's vectors may go; once per call)
+}
+
+// a grammar state as bytes: equal states, equal keys (the hash tables below)
+static std::string gram_state_key(const Grammar& st) {
+    std::string key((const char*)&st.partial.value, sizeof(st.partial.value));
+    key.append((const char*)&st.partial.n_remain, sizeof(st.partial.n_remain));
+    for (const GramStack& k : st.stacks) {
+        const uint16_t n = (uint16_t)k.size();
+        key.append((const char*)&n, sizeof(n));
+        key.append((const char*)k.data(), k.size() * sizeof(uint16_t));
+    }
+    return key;
+}
+
+// a state's words from the host, through the table of the states this call already built
+static const std::vector<uint32_t>& gram_host_mask(Context* c, GramDev& d, const GrammarRules& g, const Grammar& st) {
+    std::string key = gram_state_key(st);
+    auto it = d.host_masks.find(key);
+    if (it == d.host_masks.end()) {
+        if (d.host_masks.size() >= 256) d.host_masks.clear();
+        it = d.host_masks.emplace(std::move(key), std::vector<uint32_t>(grammar_words(c->hp.n_vocab))).first;
+        grammar_reject(g, gram_vocab(c), st, it->second.data());
+    }
+    return it->second;
+}
+
+void gram_masks(Context* c, GramDev& d, const GrammarRules& g, const Grammar* const* states, int n, uint32_t* gram,
+                uint32_t* h_stage, int* flags, hipStream_t st, whisper_state* s) {
+    if (n <= 0) return;
+    const GramTable& tab = gram_table(c);
+    const size_t W = grammar_words(c->hp.n_vocab);
+    if (n > d.cap_rows) {
+        WM_CHECK(hipStreamSynchronize(st));
+        dfree(d.rows); dfree(d.over);
+        if (d.h_rows) { WM_CHECK(hipHostFree(d.h_rows)); d.h_rows = nullptr; }
+        if (d.h_over) { WM_CHECK(hipHostFree(d.h_over)); d.h_over = nullptr; }
+        d.cap_rows = 0;
+        dalloc(d.rows, (size_t)n * sizeof(GramRow));
+        dalloc(d.over, (size_t)n * sizeof(unsigned));
+        WM_CHECK(hipHostMalloc((void**)&d.h_rows, (size_t)n * sizeof(GramRow), 0));
+        WM_CHECK(hipHostMalloc((void**)&d.h_over, (size_t)n * sizeof(unsigned), 0));
+        d.cap_rows = n;
+    }
+    int n_dev = 0;
+    std::unordered_map<std::string, int> first_row;  // of the rows the kernel takes, by state
+    for (int r = 0; r < n; r++) {
+        const Grammar& q = *states[r];
+        GramRow& row = d.h_rows[r];
+        bool fits = q.partial.n_remain == 0 && (int)q.stacks.size() <= kGramRowStacks;
+        for (size_t k = 0; fits && k < q.stacks.size(); k++) fits = (int)q.stacks[k].size() <= kGramRowDepth;
+        row.n_stacks = fits ? (int)q.stacks.size() : -1;
+        row.allow_eot = q.allow_eot();
+        row.same_as = r;
+        if (!fits) continue;
+        n_dev++;
+        row.same_as = first_row.emplace(gram_state_key(q), r).first->second;  // (the first row with this state, or r)
+        for (size_t k = 0; k < q.stacks.size(); k++) {
+            row.depth[k] = (uint8_t)q.stacks[k].size();
+            std::copy(q.stacks[k].begin(), q.stacks[k].end(), row.stk[k]);
+        }
+    }
+    if (n_dev > 0) {
+        WM_CHECK(hipMemcpyAsync(d.rows, d.h_rows, (size_t)n * sizeof(GramRow), hipMemcpyHostToDevice, st));
+        WM_CHECK(hipMemsetAsync(d.over, 0, (size_t)n * sizeof(unsigned), st));
+        {
+            KT kt(s, K_GRAMMAR, (double)n_dev * tab.eot * 8, st, s != nullptr);
+            launch_grammar_reject(tab, d.elems, d.rule_off, d.rows, n, gram, d.over, st);
+        }
+        WM_CHECK(hipMemcpyAsync(d.h_over, d.over, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));  // the one extra synchronisation of a grammar step
+    }
+    for (int r = 0; r < n; r++) {
+        const bool host_only = d.h_rows[r].n_stacks < 0;
+        const bool flagged = !host_only && d.h_over[d.h_rows[r].same_as] != 0;
+        if (flags) flags[r] = host_only ? 2 : flagged ? 1 : 0;
+        (host_only ? d.rows_host : flagged ? d.rows_patched : d.rows_device)++;
+        if (!host_only && !flagged) continue;
+        const std::vector<uint32_t>& words = gram_host_mask(c, d, g, *states[r]);
+        memcpy(h_stage + (size_t)r * W, words.data(), W * sizeof(uint32_t));
+        WM_CHECK(hipMemcpyAsync(gram + (size_t)r * W, h_stage + (size_t)r * W, W * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+}
+
 static int full_batch_one(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                           int n_jobs, bool on_device, const FullOpts& o, bool single_api) {
     WM_CHECK(hipSetDevice(c->device));
@@ -3184,6 +3383,12 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     // a pattern that does not compile ends the call before anything is encoded (the mask is cached for deny_prepare)
     if (p.suppress_nst || p.suppress_regex)
         if (const int r = deny_lookup(c, p.suppress_nst, p.suppress_regex, nullptr)) return r;
+    // a malformed or left-recursive grammar ends the call before anything is encoded
+    s->gram_on = false;
+    if (const int r = grammar_check(p, s->gram_rules)) return r;
+    s->gram_on = s->gram_rules.on();
+    s->gram_penalty = p.grammar_penalty;
+    S.gram0.init(s->gram_rules);
     ensure_expanded(c, s->stream);  // quantized files: before anything is captured
     S.hyps.resize(S.beam_k > 0 || S.sample_n > 1 ? n_jobs : 0);
     s->beam_info.assign(n_jobs, {});
@@ -3203,6 +3408,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
         ensure_ws(c, s, n_jobs * std::max(1, std::max(S.beam_k, S.sample_n)), n_jobs);
         if (!single_api) s->audio_ctx = 0;  // every clip of the batch API starts as on a fresh state (apply_audio_ctx)
         if (const int r = deny_prepare(c, s, p)) return r;
+        if (s->gram_on) gram_dev_rules(s->ws.gd, s->gram_rules, s->stream);
         compute_mel(c, s, pcm, n, n_jobs, on_device);
     }
     if (p.token_timestamps) { ScopeTimer timed{S.t_tokts}; compute_energy(s, pcm, n, n_jobs, on_device); }
@@ -3230,6 +3436,10 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
     if (const int r = check_audio_ctx(c, p.audio_ctx)) return r;  // (before the halves start: one line, not one per half)
     if (p.suppress_nst || p.suppress_regex)
         if (const int r = deny_lookup(c, p.suppress_nst, p.suppress_regex, nullptr)) return r;
+    {
+        GrammarRules rules;
+        if (const int r = grammar_check(p, rules)) return r;
+    }
     WM_CHECK(hipSetDevice(c->device));
     if (!s->twin) s->twin = create_state(c);
     whisper_state* t = s->twin;

@@ -6,11 +6,13 @@
 #include <mutex>
 #include <random>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/whisper_mi355x.h"
 #include "beam.h"
 #include "common.h"
+#include "grammar.h"
 #include "kernels.h"
 
 namespace wm {
@@ -147,7 +149,40 @@ struct Context {
     DenyKey deny_key;
     std::vector<uint32_t> deny_words;
     long deny_builds = 0;  // masks built since the context was created (whisper_mi355x_suppress_builds)
+    // The vocabulary decoded for grammar calls (grammar.h): built by the first one, under the mutex
+    std::mutex gram_mu;
+    bool gram_vocab_built = false;
+    GramVocab gram_vocab;
+    // ... and its copy on the device for the reject kernel (kernels.h GramTable; ~1 MB for large-v3's vocabulary), built
+    // with it and freed with the context
+    GramTable gram_tab{};
+    void* gram_tab_mem[4] = {nullptr, nullptr, nullptr, nullptr};
 };
+
+// The device side of a grammar call's masks (engine.cpp gram_masks): the call's flat rules, the rows' stack lists of a
+// step and the rows' overflow words, with their pinned staging. A state's workspace has one; the debug hook its own.
+struct GramDev {
+    GramElem* elems = nullptr;
+    int* rule_off = nullptr;
+    size_t cap_elems = 0, cap_rules = 0;
+    GramRow *rows = nullptr, *h_rows = nullptr;
+    unsigned *over = nullptr, *h_over = nullptr;
+    int cap_rows = 0;
+    // masks built on the host (rows the kernel does not take, rows it flagged), by serialized state; at most 256, then
+    // the table starts over
+    std::unordered_map<std::string, std::vector<uint32_t>> host_masks;
+    long rows_device = 0, rows_patched = 0, rows_host = 0;
+};
+void gram_dev_free(GramDev& d);
+// the call's rules to the device (synchronises the stream); the host-mask table starts empty
+void gram_dev_rules(GramDev& d, const GrammarRules& g, hipStream_t st);
+// The reject words of n grammar states into gram [n][grammar_words] on the device, in stream order: the kernel for the
+// rows it takes, grammar_reject on the host for rows whose stack list does not fit or whose pending partial has
+// n_remain != 0, and for rows the kernel flagged (one synchronisation to read the flags). flags (if given): 0 decided
+// by the kernel, 1 patched after overflow, 2 host only. h_stage: pinned [n][grammar_words]. s: the state whose
+// K_GRAMMAR timing the launch goes to, or null.
+void gram_masks(Context* c, GramDev& d, const GrammarRules& g, const Grammar* const* states, int n, uint32_t* gram,
+                uint32_t* h_stage, int* flags, hipStream_t st, whisper_state* s);
 
 struct TokenData {
     int id, tid;
@@ -201,6 +236,11 @@ struct Workspace {
     uint32_t* deny = nullptr;
     bool deny_held = false;
     Context::DenyKey deny_key;
+    // the grammar's reject words of a step's rows, [cap_jobs][grammar_words(n_vocab)] (grammar.h), and
+    // their pinned staging: sized with cap_jobs, so a captured step's pointer lives as long as its graph
+    uint32_t* gram = nullptr;
+    uint32_t* h_gram = nullptr;
+    GramDev gd;
     int *win_job = nullptr, *win_seek = nullptr, *win_slot = nullptr;
     // persistent decode step: the hand-off block (granules + error word) and the error word's host copy
     unsigned* pd_sync = nullptr;
@@ -256,7 +296,7 @@ struct Workspace {
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
-              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_NCLASS };
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_GRAMMAR, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 // What a decode step does besides greedy's plain step (whisper_state::mode; all off between steps). topk > 0: the
@@ -328,7 +368,9 @@ struct whisper_state {
     // direct form's slot stride of a captured step depend on it)
     // (deny: the step's logits launch reads the deny mask, whisper_state::deny_on: the pointer, or null, is a kernel
     // argument)
-    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; bool deny = false; };
+    // (gram, gram_pen: the logits launch reads the grammar's reject words, whisper_state::gram_on, and the penalty is a
+    // kernel argument)
+    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; bool deny = false; bool gram = false; float gram_pen = 0.0f; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
     double cur_self_work = 0;                     // self-attention bytes of the current step
@@ -345,6 +387,11 @@ struct whisper_state {
     wm::StepMode mode;
     // the current call has a deny mask (suppress_nst or suppress_regex is set): its logits launches read ws.deny
     bool deny_on = false;
+    // the current call has a grammar (whisper_full_params.grammar_rules): its flat rules, its penalty; its
+    // logits launches read ws.gram (the rows' counters are in ws.gd: whisper_mi355x_grammar_stats)
+    bool gram_on = false;
+    wm::GrammarRules gram_rules;
+    float gram_penalty = 0.0f;
     // beam_info[job] = the beams of the job's last beam-searched window (whisper_mi355x_beam_info)
     struct BeamRec { std::vector<int> tokens; double sum_logprobs_all = 0; int flags = 0; };
     std::vector<std::vector<BeamRec>> beam_info;
@@ -397,6 +444,11 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
 // The deny mask of (suppress_nst, regex) from the context's one-entry cache, built when the key differs: 0 and the
 // words in `words` (if given), or -8 and one stderr line when the pattern does not compile. Host only.
 int deny_lookup(Context* c, bool suppress_nst, const char* regex, std::vector<uint32_t>* words);
+// The call's grammar fields validated and flattened (grammar.h): 0 (rules off when the call has no grammar), or -9 and
+// one stderr line. Host only.
+int grammar_check(const whisper_full_params& p, GrammarRules& rules);
+// the context's decoded vocabulary, built on first use
+const GramVocab& gram_vocab(Context* c);
 
 // pieces exposed for whisper.h's low-level API
 int compute_mel(Context* c, whisper_state* s, const float* const* pcm, const int* n, int n_jobs, bool on_device);

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "gemm_plan.h"
+#include "grammar.h"
 
 namespace wm {
 
@@ -318,8 +319,13 @@ struct TokOut { int id, tid; float p, plog, pt, ptsum, nosp_prob, pad; };
 // deny: the deny mask of suppress_nst / suppress_regex on the device (suppress.h: (n_vocab + 31) / 32 words, bit
 // i & 31 of word i >> 5 = token i gets -inf like any other rule; nosp_prob stays the raw row's), or null: no mask,
 // and the launch is bit for bit the one from before the mask existed
+// gram: the grammar's reject words on the device (grammar.h, DESIGN.md §16: [n_seq][(n_vocab + 31) / 32], row r's bit
+// i = token i <= eot of row r loses gram_penalty after the timestamp rule, when that rule did not mask the text tokens,
+// and the row's log-softmax is taken again), or null: no grammar, and the launch is the one from before the rule
+// existed. With gram the launch takes the one-workgroup-per-row form whatever n_seq is (also launch_logits_topk).
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v,
-                   TokOut* out, float* probs, void* rec, const uint32_t* deny, hipStream_t st);
+                   TokOut* out, float* probs, void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty,
+                   hipStream_t st);
 size_t logits_rec_bytes(int n_seq);
 // Top-k after the rules (beam search): the k <= kTopkMax most probable tokens of every row, p > 0, in
 // (p descending, id ascending) order, as TokOut records cand[row * kTopkMax + j]; j = 0 repeats the record
@@ -327,7 +333,33 @@ size_t logits_rec_bytes(int n_seq);
 // a record j > 0 without a token has id = -1. Rows are t = 0 rows (want_probs is ignored).
 constexpr int kTopkMax = 8;
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
-                        void* rec, const uint32_t* deny, hipStream_t st);
+                        void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st);
+// ---- the grammar's reject masks (kernels/grammar.hip) -------------------------------------------------
+// What the kernel takes of a row's grammar state, and a token's working set (stacks per token, depth): a state or a
+// token's simulation beyond them is the host's (grammar_reject).
+constexpr int kGramRowStacks = 32, kGramRowDepth = 16;
+constexpr int kGramTokStacks = 8, kGramTokDepth = 16;
+static_assert(kGramTokDepth >= kGramRowDepth, "a row's stack fits a token's slot");
+constexpr int kGramTokEmpty = -2;  // GramTable::tail_rem of an id whose string is empty (never penalised)
+// (same_as: the first row of the launch with this row's state, or the row itself: the rows of a step mostly share a few
+// states, so a state is simulated once and its words are copied to the rows that share it)
+struct GramRow {  // n_stacks < 0: the row is not the kernel's (its words are left alone)
+    int n_stacks, allow_eot, same_as;
+    uint8_t depth[kGramRowStacks];
+    uint16_t stk[kGramRowStacks][kGramRowDepth];  // positions (element indices), the top last
+};
+// The vocabulary decoded once per context, on the device, for ids < eot: CSR offsets [eot + 1], the code points, and the
+// trailing partial of decode(string, {0, 0}) (tail_rem: bytes missing, -1 an invalid token, kGramTokEmpty)
+struct GramTable {
+    const uint32_t *off, *cps, *tail_val;
+    const int* tail_rem;
+    int eot, n_vocab;
+};
+// gram[row][(n_vocab + 31) / 32] of the n_rows rows (grammar.h's layout: the EOT bit = !allow_eot, bits above eot 0, a
+// row without stacks all zeros); over[row] (zeroed by the caller) becomes non-zero when a token of the row exceeded a
+// bound: that row's words are then not to be used. elems / rule_off: the call's flat rules on the device.
+void launch_grammar_reject(const GramTable& t, const GramElem* elems, const int* rule_off, const GramRow* rows, int n_rows,
+                           uint32_t* gram, unsigned* over, hipStream_t st);
 // ---- sampled draw (kernels/sample.hip; best_of candidates of a t > 0 attempt) -------
 // Row r < n (<= kSampleMaxRows, one workgroup each) draws a token from probs row src = ctr[r][3] of the
 // [.][2][n_vocab] buffer launch_logits fills for want_probs rows: uniform word x0 = words[r] if words, else

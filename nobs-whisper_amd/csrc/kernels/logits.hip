@@ -7,7 +7,8 @@
 // no_timestamps; sot/nosp/solm/translate/transcribe/prev; the 100 language tokens; the deny mask of
 // suppress_nst / suppress_regex (masked_deny; only when the call has one); timestamp
 // pairing; max_initial_ts; monotonic timestamps; log-softmax; "sum(p(timestamps)) > max p(text)
-// => timestamp"; probs = exp(logprob). Greedy argmax keeps whisper's first-index tie break over
+// => timestamp"; when that rule did not fire, the grammar's penalty on the rejected tokens and the
+// log-softmax again (gram_penalized; only when the call has a grammar); probs = exp(logprob). Greedy argmax keeps whisper's first-index tie break over
 // the float probs. When temperature > 0 the probs row is also written for host-side sampling
 // (std::discrete_distribution, exactly as whisper.cpp samples).
 // This file is compiled with -ffp-contract=off.
@@ -51,6 +52,18 @@ __device__ __forceinline__ float masked_deny(float x, int i, const SeqCtl& c, co
         if ((deny[i >> 5] >> (i & 31)) & 1u) return -INFINITY;
     }
     return masked_logit(x, i, c, v);
+}
+
+// GM: the grammar's reject mask (whisper_full_params.grammar_rules): gram = the row's words, bit i & 31 of
+// word i >> 5 set = token i <= eot loses `penalty` from its filtered logit (-inf stays -inf), after the timestamp rule
+// and only when that rule did not mask the text tokens (the callers test mask_text). 0: no grammar (gram is not read:
+// the code of a launch without one is what it was before the rule existed), 1: the device words, read through the cache.
+template <int GM>
+__device__ __forceinline__ float gram_penalized(float x, int i, const VocabIds& v, const uint32_t* gram, float penalty) {
+    if constexpr (GM != 0) {
+        if (i <= v.eot && ((gram[i >> 5] >> (i & 31)) & 1u)) return x - penalty;
+    }
+    return x;
 }
 
 __device__ float block_max(float x, float* sh) {
@@ -166,10 +179,11 @@ static size_t row_lds_bytes(int dm, int n_vocab) {
     return (size_t)NPT_LDS * LT * sizeof(float) + (dm == 2 ? (size_t)((n_vocab + 31) / 32) * sizeof(uint32_t) : 0);
 }
 
-template <int DM>
+template <int DM, int GM>
 __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
                                                     VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs,
-                                                    const uint32_t* __restrict__ deny) {
+                                                    const uint32_t* __restrict__ deny, const uint32_t* __restrict__ gram,
+                                                    float penalty) {
     const int s = blockIdx.x;
     const SeqCtl c = ctl[s];
     const float* L = logits + (long)s * ld;
@@ -234,7 +248,7 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
     for (int k = 0; k < NPT; k++)
         if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
     sm = block_sum(sm, shf);
-    const float lse = logf(sm) + mx;
+    float lse = logf(sm) + mx;
     // timestamp rule
     float mts = -INFINITY, mtext = -INFINITY;
 #pragma unroll
@@ -256,6 +270,31 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
     sts = block_sum(sts, shf);
     const float ts_logprob = sts > 0.0f ? logf(sts) + mts : -INFINITY;
     const bool mask_text = ts_logprob > mtext;
+    const uint32_t* grow = nullptr;  // the row's reject words when the grammar rule applies to it (uniform)
+    if constexpr (GM != 0) {
+        if (!mask_text) {
+            // the grammar's penalty, then the log-softmax again with the first pass's expressions: everything below
+            // (p, plog, pt, ptsum, the probs rows, the top-k rounds) is taken from the second one, as upstream does
+            grow = gram + (long)s * ((n + 31) >> 5);
+            const uint32_t* gl = grow + (tid >> 5);
+            const uint32_t gbit = 1u << (tid & 31);
+#pragma unroll
+            for (int k = 0; k < NPT; k++) {
+                const int i = tid + k * LT;
+                if (i <= v.eot && (gl[k * (LT / 32)] & gbit) != 0) x.set(k, x.get(k) - penalty);
+            }
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
+            mx = block_max(mx, shf);
+            sm = 0.0f;
+#pragma unroll
+            for (int k = 0; k < NPT; k++)
+                if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
+            sm = block_sum(sm, shf);
+            lse = logf(sm) + mx;
+        }
+    }
     // probs, argmax (all) and argmax / sum over timestamps
     float best = 0.0f, best_ts = 0.0f;
     int ibest = 0x7fffffff, its = 0x7fffffff;
@@ -286,6 +325,7 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         r.p = best;
         {
             float xv = masked_deny<DM>(L[r.id], r.id, c, v, dm);
+            if constexpr (GM != 0) { if (grow) xv = gram_penalized<GM>(xv, r.id, v, grow, penalty); }
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
         }
@@ -305,10 +345,11 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
 // tokens with p > 0 in (p descending, id ascending) order. A text candidate carries the row's tid / pt / ptsum, a
 // timestamp candidate tid = id and pt = p (as the greedy record does); when fewer than topk tokens have p > 0
 // the remaining records have id = -1. (A copy, not a template flag: the greedy kernel's code stays as it was.)
-template <int DM>
+template <int DM, int GM>
 __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
                                                          VocabIds v, TokOut* __restrict__ out, int topk,
-                                                         const uint32_t* __restrict__ deny) {
+                                                         const uint32_t* __restrict__ deny, const uint32_t* __restrict__ gram,
+                                                         float penalty) {
     const int s = blockIdx.x;
     const SeqCtl c = ctl[s];
     const float* L = logits + (long)s * ld;
@@ -374,7 +415,7 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
     for (int k = 0; k < NPT; k++)
         if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
     sm = block_sum(sm, shf);
-    const float lse = logf(sm) + mx;
+    float lse = logf(sm) + mx;
     // timestamp rule
     float mts = -INFINITY, mtext = -INFINITY;
 #pragma unroll
@@ -396,6 +437,31 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
     sts = block_sum(sts, shf);
     const float ts_logprob = sts > 0.0f ? logf(sts) + mts : -INFINITY;
     const bool mask_text = ts_logprob > mtext;
+    const uint32_t* grow = nullptr;  // the row's reject words when the grammar rule applies to it (uniform)
+    if constexpr (GM != 0) {
+        if (!mask_text) {
+            // the grammar's penalty, then the log-softmax again with the first pass's expressions: everything below
+            // (p, plog, pt, ptsum, the probs rows, the top-k rounds) is taken from the second one, as upstream does
+            grow = gram + (long)s * ((n + 31) >> 5);
+            const uint32_t* gl = grow + (tid >> 5);
+            const uint32_t gbit = 1u << (tid & 31);
+#pragma unroll
+            for (int k = 0; k < NPT; k++) {
+                const int i = tid + k * LT;
+                if (i <= v.eot && (gl[k * (LT / 32)] & gbit) != 0) x.set(k, x.get(k) - penalty);
+            }
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
+            mx = block_max(mx, shf);
+            sm = 0.0f;
+#pragma unroll
+            for (int k = 0; k < NPT; k++)
+                if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
+            sm = block_sum(sm, shf);
+            lse = logf(sm) + mx;
+        }
+    }
     // probs, argmax (all) and argmax / sum over timestamps
     float best = 0.0f, best_ts = 0.0f;
     int ibest = 0x7fffffff, its = 0x7fffffff;
@@ -422,6 +488,7 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
         r.p = best;
         {
             float xv = masked_deny<DM>(L[r.id], r.id, c, v, dm);
+            if constexpr (GM != 0) { if (grow) xv = gram_penalized<GM>(xv, r.id, v, grow, penalty); }
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
         }
@@ -462,6 +529,11 @@ __global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict
                 r.id = ij;
                 r.p = bj;
                 r.plog = masked_deny<DM>(L[ij], ij, c, v, dm) - lse;  // p > 0: the filtered logit is finite
+                // (masked_deny a second time, on thread 0 once per round: the line above stays the expression the
+                // GM = 0 kernels had before the rule existed; through a temporary their register allocation changed)
+                if constexpr (GM != 0) {
+                    if (grow) r.plog = gram_penalized<GM>(masked_deny<DM>(L[ij], ij, c, v, dm), ij, v, grow, penalty) - lse;
+                }
                 if (ij >= v.beg) { r.tid = ij; r.pt = bj; }
                 else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
             }
@@ -806,11 +878,25 @@ static int deny_mode(const uint32_t* deny) {
     return e && atoi(e) > 0 ? 1 : 2;
 }
 
+// the 1024-thread kernels by (deny form, grammar on / off)
+#define WM_LOGITS_DM_GM(KERNEL, dm, gm, ...)                                          \
+    do {                                                                               \
+        if (gm) {                                                                      \
+            if (dm == 2) KERNEL<2, 1> __VA_ARGS__;                                     \
+            else if (dm == 1) KERNEL<1, 1> __VA_ARGS__;                                \
+            else KERNEL<0, 1> __VA_ARGS__;                                             \
+        } else {                                                                       \
+            if (dm == 2) KERNEL<2, 0> __VA_ARGS__;                                     \
+            else if (dm == 1) KERNEL<1, 0> __VA_ARGS__;                                \
+            else KERNEL<0, 0> __VA_ARGS__;                                             \
+        }                                                                              \
+    } while (0)
+
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* out, float* probs,
-                   void* rec, const uint32_t* deny, hipStream_t st) {
+                   void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st) {
     if (n_seq <= 0) return;
     if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
-    if (rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
+    if (!gram && rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
         if (deny) {
             logits_part_kernel<1><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny);
             logits_combine_kernel<1><<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs, deny);
@@ -820,23 +906,22 @@ void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, c
         }
         return;
     }
+    // (a grammar call always takes the one-workgroup-per-row form: the split form has no second softmax)
     const int dm = deny_mode(deny);
     const size_t lds = row_lds_bytes(dm, v.n_vocab);
-    if (dm == 2) logits_kernel<2><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, deny);
-    else if (dm == 1) logits_kernel<1><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, deny);
-    else logits_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, nullptr);
+    WM_LOGITS_DM_GM(logits_kernel, dm, gram != nullptr, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, deny, gram, gram_penalty));
 }
 
-// Top-k after the rules: the form is chosen exactly as launch_logits chooses it for the same n_seq / rec, so
+// Top-k after the rules: the form is chosen exactly as launch_logits chooses it for the same n_seq / rec / gram, so
 // candidate 0 of a row is the TokOut launch_logits would return for it.
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
-                        void* rec, const uint32_t* deny, hipStream_t st) {
+                        void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st) {
     if (n_seq <= 0) return;
     if (k < 1 || k > kTopkMax) WM_FAIL("top-k %d outside 1..%d", k, kTopkMax);
     if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
     const int dm = deny_mode(deny);
     const size_t lds = row_lds_bytes(dm, v.n_vocab);
-    if (rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
+    if (!gram && rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
         const LogitRec* R = (const LogitRec*)rec;
         if (deny) logits_part_kernel<1><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny);
         else logits_part_kernel<0><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, nullptr);
@@ -845,10 +930,9 @@ void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_s
         else logits_topk_combine_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, nullptr);
         return;
     }
-    if (dm == 2) logits_topk_kernel<2><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, deny);
-    else if (dm == 1) logits_topk_kernel<1><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, deny);
-    else logits_topk_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, nullptr);
+    WM_LOGITS_DM_GM(logits_topk_kernel, dm, gram != nullptr, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, deny, gram, gram_penalty));
 }
+#undef WM_LOGITS_DM_GM
 
 // ---- device-side step advance (pipelined greedy decoding, engine.cpp decode_pipelined) -----------------------
 // After a decode step's logits kernel, in stream order: row r's chosen token becomes its next input and its

@@ -507,6 +507,11 @@ void free_context(Context* c) {
     if (c && c->pdec_layers) { hipSetDevice(c->device); hipFree(c->pdec_layers); c->pdec_layers = nullptr; }
     if (c && c->pdec_layers_exp) { hipSetDevice(c->device); hipFree(c->pdec_layers_exp); c->pdec_layers_exp = nullptr; }
     if (c && c->dtw_heads_dev) { hipSetDevice(c->device); hipFree(c->dtw_heads_dev); c->dtw_heads_dev = nullptr; }
+    if (c && c->gram_tab_mem[0]) {
+        hipSetDevice(c->device);
+        for (void*& q : c->gram_tab_mem) { hipFree(q); q = nullptr; }
+        c->gram_tab = GramTable{};
+    }
 }
 
 }  // namespace wm

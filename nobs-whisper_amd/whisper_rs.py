@@ -93,6 +93,46 @@ class FullParams(C.Structure):
         ("vad", C.c_bool), ("vad_model_path", C.c_char_p), ("vad_params", VadParams),
     ]
 
+    # whisper-rs: FullParams::set_grammar / set_start_rule / set_grammar_penalty
+    def set_grammar(self, rules, start_rule: int = 0) -> None:
+        """rules: a list of rules, each a list of (type, value) elements ending in (GRETYPE_END, 0) (None: a null entry),
+        or None / []: no grammar. The ctypes arrays live as long as this object (or until the next set_grammar)."""
+        self._grammar = grammar_arrays(rules) if rules else None
+        self.grammar_rules = C.cast(self._grammar[0], C.c_void_p) if self._grammar else None
+        self.n_grammar_rules = len(rules) if rules else 0
+        self.i_start_rule = start_rule
+
+    def set_start_rule(self, start_rule: int) -> None:
+        self.i_start_rule = start_rule
+
+    def set_grammar_penalty(self, penalty: float) -> None:
+        self.grammar_penalty = penalty
+
+
+GRAMMAR_ERR = -9  # whisper_full*: the grammar is malformed or left-recursive (whisper.h)
+(GRETYPE_END, GRETYPE_ALT, GRETYPE_RULE_REF, GRETYPE_CHAR, GRETYPE_CHAR_NOT, GRETYPE_CHAR_RNG_UPPER,
+ GRETYPE_CHAR_ALT) = range(7)
+
+
+class GrammarElement(C.Structure):
+    """whisper_grammar_element (include/whisper.h)."""
+    _fields_ = [("type", C.c_int), ("value", C.c_uint32)]
+
+
+def grammar_arrays(rules):
+    """A Python list of rules (each a list of (type, value), None: a null entry) as (the array of rule pointers, the
+    element arrays): whisper_full_params.grammar_rules. The caller keeps the tuple alive while the pointers are used."""
+    elems = [None if r is None else (GrammarElement * len(r))(*[GrammarElement(t, v) for t, v in r]) for r in rules]
+    ptrs = (C.POINTER(GrammarElement) * len(rules))(*[C.cast(e, C.POINTER(GrammarElement)) if e is not None else
+                                                      C.POINTER(GrammarElement)() for e in elems])
+    return ptrs, elems
+
+
+class GrammarStats(C.Structure):
+    """struct whisper_mi355x_grammar_stats (include/whisper_mi355x.h)."""
+    _fields_ = [("rows_device", C.c_long), ("rows_patched", C.c_long), ("rows_host", C.c_long), ("kernel_ms", C.c_double),
+                ("kernel_launches", C.c_long)]
+
 
 class TokenData(C.Structure):
     _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("plog", C.c_float), ("pt", C.c_float),
@@ -193,6 +233,15 @@ def lib() -> C.CDLL:
                                                        C.POINTER(C.c_uint32)]),
         "whisper_mi355x_debug_logits_topk_deny": (C.c_int, [vp, vp, C.c_int, ip, fp, C.c_int, C.c_int, C.POINTER(Cand),
                                                             C.POINTER(Cand), C.POINTER(C.c_uint32)]),
+        "whisper_mi355x_grammar_mask": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, ip, C.c_int, C.POINTER(C.c_uint32), C.c_int]),
+        "whisper_mi355x_grammar_stats": (C.c_int, [vp, C.POINTER(GrammarStats)]),
+        "whisper_mi355x_debug_grammar_reject": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, ip, ip, C.c_int,
+                                                          C.POINTER(C.c_uint32), ip]),
+        "whisper_mi355x_debug_logits_gram": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, C.POINTER(Cand), fp,
+                                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_float]),
+        "whisper_mi355x_debug_logits_topk_gram": (C.c_int, [vp, vp, C.c_int, ip, fp, C.c_int, C.c_int, C.POINTER(Cand),
+                                                            C.POINTER(Cand), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                            C.c_float]),
         "whisper_mi355x_debug_decode_advance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(Cand), ip,
                                                           C.POINTER(SeqCtl), C.POINTER(C.c_uint), C.POINTER(Cand),
                                                           C.POINTER(C.c_uint)]),
@@ -366,6 +415,43 @@ class WhisperContext:
         assert not bits[V:].any(), "bits at and above n_vocab"
         return bits[:V].astype(bool)
 
+    def grammar_mask(self, rules, start_rule: int = 0, accepted=()):
+        """whisper_mi355x_grammar_mask: the reject mask of the grammar state after init and the accepted token ids, as a
+        bool array [n_vocab] (host only), or the negative return code (-9: the grammar is refused)."""
+        import numpy as np
+        V = self.L.whisper_n_vocab(self.ptr)
+        w = np.zeros((V + 31) // 32, np.uint32)
+        arrs = grammar_arrays(rules)
+        acc = (C.c_int * max(1, len(accepted)))(*accepted)
+        rc = self.L.whisper_mi355x_grammar_mask(self.ptr, C.cast(arrs[0], C.c_void_p), len(rules), start_rule, acc,
+                                                len(accepted), w.ctypes.data_as(C.POINTER(C.c_uint32)), len(w))
+        if rc < 0:
+            return rc
+        assert rc == len(w)
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[:V].astype(bool)
+
+    def debug_grammar_reject(self, rules, start_rule, accepted_rows):
+        """whisper_mi355x_debug_grammar_reject: accepted_rows = one list of accepted token ids per row. Returns (masks as a
+        bool array [rows][n_vocab], flags [rows]) or the negative return code."""
+        import numpy as np
+        V = self.L.whisper_n_vocab(self.ptr)
+        n = len(accepted_rows)
+        W = (V + 31) // 32
+        w = np.zeros((n, W), np.uint32)
+        flat = [t for row in accepted_rows for t in row]
+        acc = (C.c_int * max(1, len(flat)))(*flat)
+        cnt = (C.c_int * n)(*[len(row) for row in accepted_rows])
+        flags = (C.c_int * n)()
+        arrs = grammar_arrays(rules)
+        rc = self.L.whisper_mi355x_debug_grammar_reject(self.ptr, C.cast(arrs[0], C.c_void_p), len(rules), start_rule, acc, cnt,
+                                                        n, w.ctypes.data_as(C.POINTER(C.c_uint32)), flags)
+        if rc < 0:
+            return rc
+        assert rc == W
+        bits = np.unpackbits(w.view(np.uint8).reshape(n, W * 4), axis=1, bitorder="little")
+        assert not bits[:, V:].any(), "bits at and above n_vocab"
+        return bits[:, :V].astype(bool), list(flags)
+
     @staticmethod
     def clip_offsets(n_samples) -> list:
         """Where each clip starts in the concatenated arrays of the two hooks below (the running offset rounded up to
@@ -521,6 +607,13 @@ class WhisperState:
                                L.whisper_mi355x_batch_segment_t1(self.ptr, job, i),
                                L.whisper_mi355x_batch_segment_text(self.ptr, job, i), toks))
         return out
+
+    def grammar_stats(self) -> dict:
+        """whisper_mi355x_grammar_stats: rows of grammar calls decided by the reject kernel, patched by the host after the
+        kernel flagged them, built by the host alone; the reject kernel's time and launches (kernel timing class 16)."""
+        st = GrammarStats()
+        assert self.L.whisper_mi355x_grammar_stats(self.ptr, C.byref(st)) == 0
+        return {k: getattr(st, k) for k, _ in GrammarStats._fields_}
 
     def beam_info(self, job: int = 0) -> list:
         """whisper_mi355x_beam_info: the beams of the job's last beam-searched window, as dicts {tokens,
