@@ -66,50 +66,40 @@ __device__ __forceinline__ float gram_penalized(float x, int i, const VocabIds& 
     return x;
 }
 
-__device__ float block_max(float x, float* sh) {
+// Reductions over a workgroup of NW waves (sh: NW elements): a butterfly within the wave, then every thread folds
+// the NW wave results in wave order. Each begins with a barrier, so sh can be reused from one call to the next.
+template <int NW>
+__device__ float blk_max(float x, float* sh) {
     for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-    const int w = threadIdx.x >> 6;
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = x;
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
     __syncthreads();
     float r = sh[0];
-    for (int i = 1; i < LT / 64; i++) r = fmaxf(r, sh[i]);
+    for (int i = 1; i < NW; i++) r = fmaxf(r, sh[i]);
     return r;
 }
-__device__ float block_sum(float x, float* sh) {
+template <int NW, typename T>  // float or double
+__device__ T blk_sum(T x, T* sh) {
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    const int w = threadIdx.x >> 6;
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = x;
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
     __syncthreads();
-    float r = 0.0f;
-    for (int i = 0; i < LT / 64; i++) r += sh[i];
-    return r;
-}
-__device__ double block_sum_d(double x, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = x;
-    __syncthreads();
-    double r = 0.0;
-    for (int i = 0; i < LT / 64; i++) r += sh[i];
+    T r = 0;
+    for (int i = 0; i < NW; i++) r += sh[i];
     return r;
 }
 // argmax with first-index tie break: (value larger) or (equal and index smaller)
-__device__ void block_argmax(float& v, int& idx, float* shv, int* shi) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o);
-        const int oi = __shfl_xor(idx, o);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    const int w = threadIdx.x >> 6;
+__device__ __forceinline__ void argmax_pair(float& v, int& ix, float ov, int oi) {
+    if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+}
+template <int NW>
+__device__ void blk_argmax(float& v, int& ix, float* shv, int* shi) {
+    for (int o = 32; o > 0; o >>= 1) argmax_pair(v, ix, __shfl_xor(v, o), __shfl_xor(ix, o));
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) { shv[w] = v; shi[w] = idx; }
+    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = v; shi[threadIdx.x >> 6] = ix; }
     __syncthreads();
-    v = shv[0]; idx = shi[0];
-    for (int i = 1; i < LT / 64; i++)
-        if (shv[i] > v || (shv[i] == v && shi[i] < idx)) { v = shv[i]; idx = shi[i]; }
+    v = shv[0]; ix = shi[0];
+    for (int i = 1; i < NW; i++) argmax_pair(v, ix, shv[i], shi[i]);
 }
 
 // Per-element exponentials over the whole row use the hardware exp2 (__expf, a few ulp): the GPU's
@@ -179,18 +169,27 @@ static size_t row_lds_bytes(int dm, int n_vocab) {
     return (size_t)NPT_LDS * LT * sizeof(float) + (dm == 2 ? (size_t)((n_vocab + 31) / 32) * sizeof(uint32_t) : 0);
 }
 
-template <int DM, int GM>
+// The one-workgroup-per-row form, greedy (TOPK false: launch_logits; out[s], and the probs rows when want_probs)
+// and for beam search (TOPK true: launch_logits_topk; probs is not read): the same passes up to the greedy record,
+// which becomes candidate 0 (out[s * kTopkMax]); then candidate j = 1 .. topk - 1 is the block
+// argmax of the same float probs after the earlier winners were struck from the row (set to -inf), i.e. the
+// tokens with p > 0 in (p descending, id ascending) order. A text candidate carries the row's tid / pt / ptsum, a
+// timestamp candidate tid = id and pt = p (as the greedy record does); when fewer than topk tokens have p > 0
+// the remaining records have id = -1.
+template <int DM, int GM, bool TOPK>
 __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
-                                                    VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs,
+                                                    VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs, int topk,
                                                     const uint32_t* __restrict__ deny, const uint32_t* __restrict__ gram,
                                                     float penalty) {
     const int s = blockIdx.x;
     const SeqCtl c = ctl[s];
     const float* L = logits + (long)s * ld;
+    constexpr int NW = LT / 64;
     const int n = v.n_vocab, tid = threadIdx.x;
-    __shared__ float shf[LT / 64];
-    __shared__ int shi[LT / 64];
-    __shared__ double shd[LT / 64];
+    __shared__ float shf[NW];
+    __shared__ int shi[NW];
+    __shared__ double shd[NW];
+    __shared__ TokOut s_top[2];  // TOPK: the greedy record; [1].tid / .pt: the row's tid / pt (a text candidate's)
 
     extern __shared__ float s_row[];  // [NPT_LDS][LT]
     RowSlice x{s_row};
@@ -221,12 +220,12 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
 #pragma unroll
         for (int k = 0; k < NPT; k++)
             if (tid + k * LT < n) mx = fmaxf(mx, x.get(k));
-        mx = block_max(mx, shf);
+        mx = blk_max<NW>(mx, shf);
         float sm = 0.0f;
 #pragma unroll
         for (int k = 0; k < NPT; k++)
             if (tid + k * LT < n) sm += __expf(x.get(k) - mx);
-        sm = block_sum(sm, shf);
+        sm = blk_sum<NW>(sm, shf);
         const float lse = logf(sm) + mx;
         nosp_prob = expf(L[v.nosp] - lse);
     }
@@ -242,12 +241,12 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
     float mx = -INFINITY;
 #pragma unroll
     for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
-    mx = block_max(mx, shf);
+    mx = blk_max<NW>(mx, shf);
     float sm = 0.0f;
 #pragma unroll
     for (int k = 0; k < NPT; k++)
         if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
-    sm = block_sum(sm, shf);
+    sm = blk_sum<NW>(sm, shf);
     float lse = logf(sm) + mx;
     // timestamp rule
     float mts = -INFINITY, mtext = -INFINITY;
@@ -257,8 +256,8 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         const float lp = x.get(k) > -INFINITY ? x.get(k) - lse : -INFINITY;
         if (i >= v.beg) mts = fmaxf(mts, lp); else mtext = fmaxf(mtext, lp);
     }
-    mts = block_max(mts, shf);
-    mtext = block_max(mtext, shf);
+    mts = blk_max<NW>(mts, shf);
+    mtext = blk_max<NW>(mtext, shf);
     float sts = 0.0f;
 #pragma unroll
     for (int k = 0; k < NPT; k++) {
@@ -267,7 +266,7 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         const float lp = x.get(k) > -INFINITY ? x.get(k) - lse : -INFINITY;
         if (lp > -INFINITY) sts += expf(lp - mts);  // libm-accurate: this sum decides the timestamp rule
     }
-    sts = block_sum(sts, shf);
+    sts = blk_sum<NW>(sts, shf);
     const float ts_logprob = sts > 0.0f ? logf(sts) + mts : -INFINITY;
     const bool mask_text = ts_logprob > mtext;
     const uint32_t* grow = nullptr;  // the row's reject words when the grammar rule applies to it (uniform)
@@ -286,12 +285,12 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
             mx = -INFINITY;
 #pragma unroll
             for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
-            mx = block_max(mx, shf);
+            mx = blk_max<NW>(mx, shf);
             sm = 0.0f;
 #pragma unroll
             for (int k = 0; k < NPT; k++)
                 if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
-            sm = block_sum(sm, shf);
+            sm = blk_sum<NW>(sm, shf);
             lse = logf(sm) + mx;
         }
     }
@@ -306,9 +305,11 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         float xv = x.get(k);
         if (mask_text && i < v.beg) xv = -INFINITY;
         const float p = xv == -INFINITY ? 0.0f : __expf(xv - lse);
-        if (c.want_probs) {  // [seq][2][V]: probs, logprobs (host sampling at t > 0)
-            probs[(long)s * 2 * n + i] = p;
-            probs[(long)s * 2 * n + n + i] = xv == -INFINITY ? -INFINITY : xv - lse;
+        if constexpr (!TOPK) {
+            if (c.want_probs) {  // [seq][2][V]: probs, logprobs (host sampling at t > 0)
+                probs[(long)s * 2 * n + i] = p;
+                probs[(long)s * 2 * n + n + i] = xv == -INFINITY ? -INFINITY : xv - lse;
+            }
         }
         if (p > best) { best = p; ibest = i; }
         if (i >= v.beg) {
@@ -316,9 +317,9 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
             if (p > best_ts) { best_ts = p; its = i; }
         }
     }
-    block_argmax(best, ibest, shf, shi);
-    block_argmax(best_ts, its, shf, shi);
-    sum_ts = block_sum_d(sum_ts, shd);
+    blk_argmax<NW>(best, ibest, shf, shi);
+    blk_argmax<NW>(best_ts, its, shf, shi);
+    sum_ts = blk_sum<NW>(sum_ts, shd);
     if (tid == 0) {
         TokOut r;
         r.id = best > 0.0f ? ibest : 0;
@@ -332,215 +333,56 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         r.tid = best_ts > 0.0f ? its : 0;
         r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
         r.ptsum = (float)sum_ts;
+        if constexpr (TOPK) {
+            s_top[1].tid = r.tid;
+            s_top[1].pt = r.pt;
+        }
         if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
         r.nosp_prob = nosp_prob;
         r.pad = 0.0f;
-        out[s] = r;
+        out[TOPK ? (long)s * kTopkMax : s] = r;
+        if constexpr (TOPK) s_top[0] = r;
     }
-}
-
-// logits_kernel for beam search (kernels.h launch_logits_topk): the same passes and expressions up to
-// the greedy record, which becomes candidate 0 (out[s * kTopkMax]); then candidate j = 1 .. topk - 1 is the block
-// argmax of the same float probs after the earlier winners were struck from the row (set to -inf), i.e. the
-// tokens with p > 0 in (p descending, id ascending) order. A text candidate carries the row's tid / pt / ptsum, a
-// timestamp candidate tid = id and pt = p (as the greedy record does); when fewer than topk tokens have p > 0
-// the remaining records have id = -1. (A copy, not a template flag: the greedy kernel's code stays as it was.)
-template <int DM, int GM>
-__global__ void __launch_bounds__(LT) logits_topk_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
-                                                         VocabIds v, TokOut* __restrict__ out, int topk,
-                                                         const uint32_t* __restrict__ deny, const uint32_t* __restrict__ gram,
-                                                         float penalty) {
-    const int s = blockIdx.x;
-    const SeqCtl c = ctl[s];
-    const float* L = logits + (long)s * ld;
-    const int n = v.n_vocab, tid = threadIdx.x;
-    __shared__ float shf[LT / 64];
-    __shared__ int shi[LT / 64];
-    __shared__ double shd[LT / 64];
-    __shared__ TokOut s_top[2];  // the greedy record; [1].tid / .pt: the row's tid / pt (a text candidate's)
-
-    extern __shared__ float s_row[];  // [NPT_LDS][LT]
-    RowSlice x{s_row};
-    DenyLane<DM> dl;
-    dl.load(deny, s_row, n);
-    const uint32_t* dm = dl.words;
-    // the register part first, then the LDS part in batches of 12 loads in flight (a load -> LDS
-    // store pair per element would wait out one memory latency per element)
+    if constexpr (TOPK) {
+        // best / ibest are the block's in every thread: each round strikes the last winner from the row
+        for (int j = 1; j < topk; j++) {
+            const bool dead = !(best > 0.0f);  // no token with p > 0 is left (uniform)
+            float bj = 0.0f;
+            int ij = 0x7fffffff;
+            if (!dead) {
 #pragma unroll
-    for (int k = NPT_LDS; k < NPT; k++) {
-        const int i = tid + k * LT;
-        x.set(k, i < n ? L[i] : -INFINITY);
-    }
-#pragma unroll
-    for (int k0 = 0; k0 < NPT_LDS; k0 += 12) {
-        float t[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) {
-            const int i = tid + (k0 + k) * LT;
-            t[k] = i < n ? L[i] : -INFINITY;
-        }
-#pragma unroll
-        for (int k = 0; k < 12; k++) x.set(k0 + k, t[k]);
-    }
-    float nosp_prob = 0.0f;
-    if (c.want_nosp) {  // no-speech probability from the raw (unfiltered) logits
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < NPT; k++)
-            if (tid + k * LT < n) mx = fmaxf(mx, x.get(k));
-        mx = block_max(mx, shf);
-        float sm = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NPT; k++)
-            if (tid + k * LT < n) sm += __expf(x.get(k) - mx);
-        sm = block_sum(sm, shf);
-        const float lse = logf(sm) + mx;
-        nosp_prob = expf(L[v.nosp] - lse);
-    }
-    // filtered logits, in place
-    dl.store(s_row, n);
-    if constexpr (DM == 2) __syncthreads();  // the mask's LDS copy
-#pragma unroll
-    for (int k = 0; k < NPT; k++) {
-        const int i = tid + k * LT;
-        if (i < n) x.set(k, dl.denied(k) ? -INFINITY : masked_logit(x.get(k), i, c, v));
-    }
-    // log-softmax of the filtered logits
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
-    mx = block_max(mx, shf);
-    float sm = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NPT; k++)
-        if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
-    sm = block_sum(sm, shf);
-    float lse = logf(sm) + mx;
-    // timestamp rule
-    float mts = -INFINITY, mtext = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < NPT; k++) {
-        const int i = tid + k * LT;
-        const float lp = x.get(k) > -INFINITY ? x.get(k) - lse : -INFINITY;
-        if (i >= v.beg) mts = fmaxf(mts, lp); else mtext = fmaxf(mtext, lp);
-    }
-    mts = block_max(mts, shf);
-    mtext = block_max(mtext, shf);
-    float sts = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NPT; k++) {
-        const int i = tid + k * LT;
-        if (i < v.beg) continue;
-        const float lp = x.get(k) > -INFINITY ? x.get(k) - lse : -INFINITY;
-        if (lp > -INFINITY) sts += expf(lp - mts);  // libm-accurate: this sum decides the timestamp rule
-    }
-    sts = block_sum(sts, shf);
-    const float ts_logprob = sts > 0.0f ? logf(sts) + mts : -INFINITY;
-    const bool mask_text = ts_logprob > mtext;
-    const uint32_t* grow = nullptr;  // the row's reject words when the grammar rule applies to it (uniform)
-    if constexpr (GM != 0) {
-        if (!mask_text) {
-            // the grammar's penalty, then the log-softmax again with the first pass's expressions: everything below
-            // (p, plog, pt, ptsum, the probs rows, the top-k rounds) is taken from the second one, as upstream does
-            grow = gram + (long)s * ((n + 31) >> 5);
-            const uint32_t* gl = grow + (tid >> 5);
-            const uint32_t gbit = 1u << (tid & 31);
-#pragma unroll
-            for (int k = 0; k < NPT; k++) {
-                const int i = tid + k * LT;
-                if (i <= v.eot && (gl[k * (LT / 32)] & gbit) != 0) x.set(k, x.get(k) - penalty);
-            }
-            mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < NPT; k++) mx = fmaxf(mx, x.get(k));
-            mx = block_max(mx, shf);
-            sm = 0.0f;
-#pragma unroll
-            for (int k = 0; k < NPT; k++)
-                if (x.get(k) > -INFINITY) sm += __expf(x.get(k) - mx);
-            sm = block_sum(sm, shf);
-            lse = logf(sm) + mx;
-        }
-    }
-    // probs, argmax (all) and argmax / sum over timestamps
-    float best = 0.0f, best_ts = 0.0f;
-    int ibest = 0x7fffffff, its = 0x7fffffff;
-    double sum_ts = 0.0;
-#pragma unroll
-    for (int k = 0; k < NPT; k++) {
-        const int i = tid + k * LT;
-        if (i >= n) continue;
-        float xv = x.get(k);
-        if (mask_text && i < v.beg) xv = -INFINITY;
-        const float p = xv == -INFINITY ? 0.0f : __expf(xv - lse);
-        if (p > best) { best = p; ibest = i; }
-        if (i >= v.beg) {
-            sum_ts += (double)p;
-            if (p > best_ts) { best_ts = p; its = i; }
-        }
-    }
-    block_argmax(best, ibest, shf, shi);
-    block_argmax(best_ts, its, shf, shi);
-    sum_ts = block_sum_d(sum_ts, shd);
-    if (tid == 0) {
-        TokOut r;
-        r.id = best > 0.0f ? ibest : 0;
-        r.p = best;
-        {
-            float xv = masked_deny<DM>(L[r.id], r.id, c, v, dm);
-            if constexpr (GM != 0) { if (grow) xv = gram_penalized<GM>(xv, r.id, v, grow, penalty); }
-            if (mask_text && r.id < v.beg) xv = -INFINITY;
-            r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
-        }
-        r.tid = best_ts > 0.0f ? its : 0;
-        r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
-        r.ptsum = (float)sum_ts;
-        s_top[1].tid = r.tid;
-        s_top[1].pt = r.pt;
-        if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
-        r.nosp_prob = nosp_prob;
-        r.pad = 0.0f;
-        out[(long)s * kTopkMax] = r;
-        s_top[0] = r;
-    }
-    // best / ibest are the block's in every thread: each round strikes the last winner from the row
-    for (int j = 1; j < topk; j++) {
-        const bool dead = !(best > 0.0f);  // no token with p > 0 is left (uniform)
-        float bj = 0.0f;
-        int ij = 0x7fffffff;
-        if (!dead) {
-#pragma unroll
-            for (int k = 0; k < NPT; k++) {
-                const int i = tid + k * LT;
-                if (i == ibest) x.set(k, -INFINITY);
-                if (i >= n) continue;
-                float xv = x.get(k);
-                if (mask_text && i < v.beg) xv = -INFINITY;
-                const float p = xv == -INFINITY ? 0.0f : __expf(xv - lse);
-                if (p > bj) { bj = p; ij = i; }
-            }
-        }
-        block_argmax(bj, ij, shf, shi);  // (its first barrier also orders s_top against thread 0's reads below)
-        if (tid == 0) {
-            TokOut r = s_top[0];
-            if (!(bj > 0.0f)) {
-                r.id = -1; r.tid = 0; r.p = 0.0f; r.plog = -INFINITY; r.pt = 0.0f;
-            } else {
-                r.id = ij;
-                r.p = bj;
-                r.plog = masked_deny<DM>(L[ij], ij, c, v, dm) - lse;  // p > 0: the filtered logit is finite
-                // (masked_deny a second time, on thread 0 once per round: the line above stays the expression the
-                // GM = 0 kernels had before the rule existed; through a temporary their register allocation changed)
-                if constexpr (GM != 0) {
-                    if (grow) r.plog = gram_penalized<GM>(masked_deny<DM>(L[ij], ij, c, v, dm), ij, v, grow, penalty) - lse;
+                for (int k = 0; k < NPT; k++) {
+                    const int i = tid + k * LT;
+                    if (i == ibest) x.set(k, -INFINITY);
+                    if (i >= n) continue;
+                    float xv = x.get(k);
+                    if (mask_text && i < v.beg) xv = -INFINITY;
+                    const float p = xv == -INFINITY ? 0.0f : __expf(xv - lse);
+                    if (p > bj) { bj = p; ij = i; }
                 }
-                if (ij >= v.beg) { r.tid = ij; r.pt = bj; }
-                else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
             }
-            out[(long)s * kTopkMax + j] = r;
+            blk_argmax<NW>(bj, ij, shf, shi);  // (its first barrier also orders s_top against thread 0's reads below)
+            if (tid == 0) {
+                TokOut r = s_top[0];
+                if (!(bj > 0.0f)) {
+                    r.id = -1; r.tid = 0; r.p = 0.0f; r.plog = -INFINITY; r.pt = 0.0f;
+                } else {
+                    r.id = ij;
+                    r.p = bj;
+                    r.plog = masked_deny<DM>(L[ij], ij, c, v, dm) - lse;  // p > 0: the filtered logit is finite
+                    // (masked_deny a second time, on thread 0 once per round, not a temporary shared with the line
+                    // above: through one the GM = 0 instantiations' register allocation changed)
+                    if constexpr (GM != 0) {
+                        if (grow) r.plog = gram_penalized<GM>(masked_deny<DM>(L[ij], ij, c, v, dm), ij, v, grow, penalty) - lse;
+                    }
+                    if (ij >= v.beg) { r.tid = ij; r.pt = bj; }
+                    else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
+                }
+                out[(long)s * kTopkMax + j] = r;
+            }
+            best = bj;
+            ibest = ij;
         }
-        best = bj;
-        ibest = ij;
     }
 }
 
@@ -563,40 +405,6 @@ struct LogitRec {
 };
 
 size_t logits_rec_bytes(int n_seq) { return (size_t)std::max(1, n_seq) * KS * sizeof(LogitRec); }
-
-__device__ __forceinline__ void argmax_pair(float& v, int& ix, float ov, int oi) {
-    if (ov > v || (ov == v && oi < ix)) { v = ov; ix = oi; }
-}
-
-template <int NW>
-__device__ float blk_max(float x, float* sh) {
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    float r = sh[0];
-    for (int i = 1; i < NW; i++) r = fmaxf(r, sh[i]);
-    return r;
-}
-template <int NW>
-__device__ float blk_sum(float x, float* sh) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-    __syncthreads();
-    float r = 0.0f;
-    for (int i = 0; i < NW; i++) r += sh[i];
-    return r;
-}
-template <int NW>
-__device__ void blk_argmax(float& v, int& ix, float* shv, int* shi) {
-    for (int o = 32; o > 0; o >>= 1) argmax_pair(v, ix, __shfl_xor(v, o), __shfl_xor(ix, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = v; shi[threadIdx.x >> 6] = ix; }
-    __syncthreads();
-    v = shv[0]; ix = shi[0];
-    for (int i = 1; i < NW; i++) argmax_pair(v, ix, shv[i], shi[i]);
-}
 
 // (DM 0 / 1 in the split form's 256-thread kernels: a chunk workgroup needs ~102 words of the mask once each, so
 // they come through the cache)
@@ -672,6 +480,67 @@ __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restric
     if (tid == 0) rec[(long)s * KS + c] = r;
 }
 
+// Pass 2's combine of a row's KS chunk records, in chunk order, by one thread (thread 0 of either combine kernel):
+// the greedy record, and what the kernels' other passes need.
+struct RowRec {
+    TokOut r;
+    float lse;
+    bool mask_text;
+    int win;   // the winner's id, -1: no token has p > 0
+    int tid;   // the row's tid / pt (a text candidate's)
+    float pt;
+};
+template <int DM>
+__device__ __forceinline__ RowRec combine_recs(const float* L, int s, const SeqCtl& q, const VocabIds& v, const LogitRec* rec,
+                                               const uint32_t* dm) {
+    const LogitRec* R = rec + (long)s * KS;
+    float M = -INFINITY, Mts = -INFINITY, Mtx = -INFINITY, Mr = -INFINITY;
+    int ix = 0x7fffffff, its = 0x7fffffff;
+    for (int c = 0; c < KS; c++) {
+        argmax_pair(M, ix, R[c].m, R[c].ix_all);
+        argmax_pair(Mts, its, R[c].m_ts, R[c].ix_ts);
+        Mtx = fmaxf(Mtx, R[c].m_text);
+        Mr = fmaxf(Mr, R[c].m_r);
+    }
+    float S = 0.0f, Sts = 0.0f, Sr = 0.0f;
+    for (int c = 0; c < KS; c++) {
+        if (R[c].m > -INFINITY) S += R[c].s * expf(R[c].m - M);
+        if (R[c].m_ts > -INFINITY) Sts += R[c].s_ts * expf(R[c].m_ts - Mts);
+        if (q.want_nosp && R[c].m_r > -INFINITY) Sr += R[c].s_r * expf(R[c].m_r - Mr);
+    }
+    RowRec o;
+    const float lse = logf(S) + M;
+    const float mts = Mts - lse, mtext = Mtx - lse;
+    const float ts_logprob = Sts > 0.0f ? logf(Sts) + mts : -INFINITY;
+    const bool mask_text = ts_logprob > mtext;
+    TokOut r;
+    const float xb = mask_text ? Mts : M;
+    const int ib = mask_text ? its : ix;
+    const float best = xb > -INFINITY ? __expf(xb - lse) : 0.0f;
+    r.id = best > 0.0f ? ib : 0;
+    r.p = best;
+    {
+        float xv = masked_deny<DM>(L[r.id], r.id, q, v, dm);
+        if (mask_text && r.id < v.beg) xv = -INFINITY;
+        r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
+    }
+    const float best_ts = Mts > -INFINITY ? __expf(Mts - lse) : 0.0f;
+    const double sum_ts = Mts > -INFINITY ? (double)Sts * (double)expf(Mts - lse) : 0.0;
+    r.tid = best_ts > 0.0f ? its : 0;
+    r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
+    r.ptsum = (float)sum_ts;
+    o.tid = r.tid;
+    o.pt = r.pt;
+    if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
+    r.nosp_prob = q.want_nosp ? expf(L[v.nosp] - (logf(Sr) + Mr)) : 0.0f;
+    r.pad = 0.0f;
+    o.r = r;
+    o.lse = lse;
+    o.mask_text = mask_text;
+    o.win = best > 0.0f ? ib : -1;
+    return o;
+}
+
 template <int DM>
 __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __restrict__ logits, long ld,
                                                              const SeqCtl* __restrict__ ctl, VocabIds v,
@@ -683,47 +552,10 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
     __shared__ float sh_lse;
     __shared__ int sh_mask;
     if (tid == 0) {
-        const LogitRec* R = rec + (long)s * KS;
-        float M = -INFINITY, Mts = -INFINITY, Mtx = -INFINITY, Mr = -INFINITY;
-        int ix = 0x7fffffff, its = 0x7fffffff;
-        for (int c = 0; c < KS; c++) {
-            argmax_pair(M, ix, R[c].m, R[c].ix_all);
-            argmax_pair(Mts, its, R[c].m_ts, R[c].ix_ts);
-            Mtx = fmaxf(Mtx, R[c].m_text);
-            Mr = fmaxf(Mr, R[c].m_r);
-        }
-        float S = 0.0f, Sts = 0.0f, Sr = 0.0f;
-        for (int c = 0; c < KS; c++) {
-            if (R[c].m > -INFINITY) S += R[c].s * expf(R[c].m - M);
-            if (R[c].m_ts > -INFINITY) Sts += R[c].s_ts * expf(R[c].m_ts - Mts);
-            if (q.want_nosp && R[c].m_r > -INFINITY) Sr += R[c].s_r * expf(R[c].m_r - Mr);
-        }
-        const float lse = logf(S) + M;
-        const float mts = Mts - lse, mtext = Mtx - lse;
-        const float ts_logprob = Sts > 0.0f ? logf(Sts) + mts : -INFINITY;
-        const bool mask_text = ts_logprob > mtext;
-        TokOut r;
-        const float xb = mask_text ? Mts : M;
-        const int ib = mask_text ? its : ix;
-        const float best = xb > -INFINITY ? __expf(xb - lse) : 0.0f;
-        r.id = best > 0.0f ? ib : 0;
-        r.p = best;
-        {
-            float xv = masked_deny<DM>(L[r.id], r.id, q, v, dm);
-            if (mask_text && r.id < v.beg) xv = -INFINITY;
-            r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
-        }
-        const float best_ts = Mts > -INFINITY ? __expf(Mts - lse) : 0.0f;
-        const double sum_ts = Mts > -INFINITY ? (double)Sts * (double)expf(Mts - lse) : 0.0;
-        r.tid = best_ts > 0.0f ? its : 0;
-        r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
-        r.ptsum = (float)sum_ts;
-        if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
-        r.nosp_prob = q.want_nosp ? expf(L[v.nosp] - (logf(Sr) + Mr)) : 0.0f;
-        r.pad = 0.0f;
-        out[s] = r;
-        sh_lse = lse;
-        sh_mask = mask_text;
+        const RowRec c = combine_recs<DM>(L, s, q, v, rec, dm);
+        out[s] = c.r;
+        sh_lse = c.lse;
+        sh_mask = c.mask_text;
     }
     if (!q.want_probs) return;
     __syncthreads();
@@ -737,9 +569,9 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
     }
 }
 
-// The split form's pass 2 for top-k rows (beam search): thread 0 combines the chunk records exactly as
-// logits_combine_kernel does (the same expressions in the same order, so candidate 0 is that kernel's record
-// bit for bit), while the 1024 threads hold the filtered row in LDS / registers as logits_kernel does. Candidate
+// The split form's pass 2 for top-k rows (beam search): thread 0 combines the chunk records with combine_recs, as
+// logits_combine_kernel does (one function, so candidate 0 is that kernel's record bit for bit), while the 1024
+// threads hold the filtered row in LDS / registers as logits_kernel does. Candidate
 // j > 0 is the block argmax of the filtered logits x (lowest index on ties; text tokens excluded when the
 // timestamp rule fired) without the earlier winners, with p = e^(x - lse), plog = x - lse: the split form's own
 // key (it orders by x where the one-workgroup form orders by the rounded p). A candidate whose p underflows
@@ -752,8 +584,9 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
     const int s = blockIdx.x, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
     const float* L = logits + (long)s * ld;
-    __shared__ float shf[LT / 64];
-    __shared__ int shi[LT / 64];
+    constexpr int NW = LT / 64;
+    __shared__ float shf[NW];
+    __shared__ int shi[NW];
     __shared__ float sh_lse;
     __shared__ int sh_mask;
     __shared__ TokOut s_top[2];  // candidate 0; [1].tid / .pt: the row's tid / pt (a text candidate's)
@@ -785,51 +618,14 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
         }
     }
     if (tid == 0) {
-        const LogitRec* R = rec + (long)s * KS;
-        float M = -INFINITY, Mts = -INFINITY, Mtx = -INFINITY, Mr = -INFINITY;
-        int ix = 0x7fffffff, its = 0x7fffffff;
-        for (int c = 0; c < KS; c++) {
-            argmax_pair(M, ix, R[c].m, R[c].ix_all);
-            argmax_pair(Mts, its, R[c].m_ts, R[c].ix_ts);
-            Mtx = fmaxf(Mtx, R[c].m_text);
-            Mr = fmaxf(Mr, R[c].m_r);
-        }
-        float S = 0.0f, Sts = 0.0f, Sr = 0.0f;
-        for (int c = 0; c < KS; c++) {
-            if (R[c].m > -INFINITY) S += R[c].s * expf(R[c].m - M);
-            if (R[c].m_ts > -INFINITY) Sts += R[c].s_ts * expf(R[c].m_ts - Mts);
-            if (q.want_nosp && R[c].m_r > -INFINITY) Sr += R[c].s_r * expf(R[c].m_r - Mr);
-        }
-        const float lse = logf(S) + M;
-        const float mts = Mts - lse, mtext = Mtx - lse;
-        const float ts_logprob = Sts > 0.0f ? logf(Sts) + mts : -INFINITY;
-        const bool mask_text = ts_logprob > mtext;
-        TokOut r;
-        const float xb = mask_text ? Mts : M;
-        const int ib = mask_text ? its : ix;
-        const float best = xb > -INFINITY ? __expf(xb - lse) : 0.0f;
-        r.id = best > 0.0f ? ib : 0;
-        r.p = best;
-        {
-            float xv = masked_deny<DM>(L[r.id], r.id, q, v, dm);
-            if (mask_text && r.id < v.beg) xv = -INFINITY;
-            r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
-        }
-        const float best_ts = Mts > -INFINITY ? __expf(Mts - lse) : 0.0f;
-        const double sum_ts = Mts > -INFINITY ? (double)Sts * (double)expf(Mts - lse) : 0.0;
-        r.tid = best_ts > 0.0f ? its : 0;
-        r.pt = (float)((double)best_ts / (sum_ts + 1e-10));
-        r.ptsum = (float)sum_ts;
-        s_top[1].tid = r.tid;
-        s_top[1].pt = r.pt;
-        if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
-        r.nosp_prob = q.want_nosp ? expf(L[v.nosp] - (logf(Sr) + Mr)) : 0.0f;
-        r.pad = 0.0f;
-        cand[(long)s * kTopkMax] = r;
-        s_top[0] = r;
-        sh_win = best > 0.0f ? ib : -1;
-        sh_lse = lse;
-        sh_mask = mask_text;
+        const RowRec c = combine_recs<DM>(L, s, q, v, rec, dm);
+        s_top[1].tid = c.tid;
+        s_top[1].pt = c.pt;
+        cand[(long)s * kTopkMax] = c.r;
+        s_top[0] = c.r;
+        sh_win = c.win;
+        sh_lse = c.lse;
+        sh_mask = c.mask_text;
     }
     __syncthreads();
     const float lse = sh_lse;
@@ -848,7 +644,7 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
                 if (xv > bj) { bj = xv; ij = i; }
             }
         }
-        block_argmax(bj, ij, shf, shi);
+        blk_argmax<NW>(bj, ij, shf, shi);
         const float p = bj > -INFINITY ? __expf(bj - lse) : 0.0f;
         if (tid == 0) {
             TokOut r = s_top[0];
@@ -878,17 +674,17 @@ static int deny_mode(const uint32_t* deny) {
     return e && atoi(e) > 0 ? 1 : 2;
 }
 
-// the 1024-thread kernels by (deny form, grammar on / off)
-#define WM_LOGITS_DM_GM(KERNEL, dm, gm, ...)                                          \
+// logits_kernel by (deny form, grammar on / off, greedy / top-k)
+#define WM_LOGITS_DM_GM(dm, gm, TOPK, ...)                                             \
     do {                                                                               \
         if (gm) {                                                                      \
-            if (dm == 2) KERNEL<2, 1> __VA_ARGS__;                                     \
-            else if (dm == 1) KERNEL<1, 1> __VA_ARGS__;                                \
-            else KERNEL<0, 1> __VA_ARGS__;                                             \
+            if (dm == 2) logits_kernel<2, 1, TOPK> __VA_ARGS__;                        \
+            else if (dm == 1) logits_kernel<1, 1, TOPK> __VA_ARGS__;                   \
+            else logits_kernel<0, 1, TOPK> __VA_ARGS__;                                \
         } else {                                                                       \
-            if (dm == 2) KERNEL<2, 0> __VA_ARGS__;                                     \
-            else if (dm == 1) KERNEL<1, 0> __VA_ARGS__;                                \
-            else KERNEL<0, 0> __VA_ARGS__;                                             \
+            if (dm == 2) logits_kernel<2, 0, TOPK> __VA_ARGS__;                        \
+            else if (dm == 1) logits_kernel<1, 0, TOPK> __VA_ARGS__;                   \
+            else logits_kernel<0, 0, TOPK> __VA_ARGS__;                                \
         }                                                                              \
     } while (0)
 
@@ -909,7 +705,7 @@ void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, c
     // (a grammar call always takes the one-workgroup-per-row form: the split form has no second softmax)
     const int dm = deny_mode(deny);
     const size_t lds = row_lds_bytes(dm, v.n_vocab);
-    WM_LOGITS_DM_GM(logits_kernel, dm, gram != nullptr, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, deny, gram, gram_penalty));
+    WM_LOGITS_DM_GM(dm, gram != nullptr, false, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, 1, deny, gram, gram_penalty));
 }
 
 // Top-k after the rules: the form is chosen exactly as launch_logits chooses it for the same n_seq / rec / gram, so
@@ -930,7 +726,7 @@ void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_s
         else logits_topk_combine_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, nullptr);
         return;
     }
-    WM_LOGITS_DM_GM(logits_topk_kernel, dm, gram != nullptr, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, k, deny, gram, gram_penalty));
+    WM_LOGITS_DM_GM(dm, gram != nullptr, true, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, nullptr, k, deny, gram, gram_penalty));
 }
 #undef WM_LOGITS_DM_GM
 

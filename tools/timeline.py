@@ -1,6 +1,8 @@
 """Decode-step timeline from a rocprofv3 --kernel-trace result (SQLite .db): for the last decode
-step of the run (the dispatches between the last two logits_kernel launches), each kernel in
-order with its duration and the idle gap before it, then per-kernel-name sums over the step.
+step of the run (the dispatches between the last two logits_kernel launches: the greedy and, since
+the row kernel is one template, the top-k instantiations alike; the split form's kernels do not
+match), each kernel in order with its duration and the idle gap before it, then per-kernel-name sums
+over the step.
 Usage: python tools/timeline.py <dir with *.db> [out.md]"""
 import glob
 import os
