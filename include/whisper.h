@@ -50,7 +50,18 @@
  * not follow a char class) or a left-recursive one (upstream recurses without end) makes whisper_full* return -9 before
  * anything is encoded, with one line on stderr.
  *
- * Still accepted and ignored: tdrz_enable and vad (with vad_model_path and vad_params).
+ * whisper_full_params.vad, vad_model_path and vad_params are implemented, and so is the whisper_vad_* block below
+ * (whisper_mi355x.h): Silero VAD v5 (16 kHz) runs on the device ahead of the mel, whisper_full*,
+ * whisper_full_parallel and whisper_mi355x_full_batch* transcribe the speech pieces only (laid end to end with 0.1 s of
+ * silence between them; offset_ms / duration_ms apply to that filtered audio), and every segment and token time is mapped
+ * back to the original audio. A clip in which no speech is found yields zero segments and 0. A null, unreadable or refused
+ * vad_model_path makes whisper_full* return -11 before anything is encoded, with one line on stderr. The loaded VAD model
+ * is cached per whisper_context, keyed by the path (upstream keeps it per state). vad == false (the default): the call
+ * runs as before and launches no VAD kernel. The model file is ggml's legacy container as upstream's
+ * convert-silero-vad-to-ggml.py writes it, restated in tools/make_vad_model.py; like the struct layouts, that layout
+ * could not be checked against a real file offline.
+ *
+ * Still accepted and ignored: tdrz_enable.
  */
 #ifndef WHISPER_H
 #define WHISPER_H
@@ -174,6 +185,15 @@ typedef struct whisper_vad_params {
     int   speech_pad_ms;
     float samples_overlap;
 } whisper_vad_params;
+
+struct whisper_vad_context;
+struct whisper_vad_segments;
+
+typedef struct whisper_vad_context_params {
+    int  n_threads;
+    bool use_gpu;     /* accepted and ignored: the device path is the only one */
+    int  gpu_device;
+} whisper_vad_context_params;
 
 enum whisper_sampling_strategy {
     WHISPER_SAMPLING_GREEDY,
@@ -383,6 +403,29 @@ WHISPER_API float whisper_full_get_token_p(struct whisper_context * ctx, int i_s
 WHISPER_API float whisper_full_get_token_p_from_state(struct whisper_state * state, int i_segment, int i_token);
 WHISPER_API float whisper_full_get_segment_no_speech_prob(struct whisper_context * ctx, int i_segment);
 WHISPER_API float whisper_full_get_segment_no_speech_prob_from_state(struct whisper_state * state, int i_segment);
+
+/* ---- voice activity detection (Silero VAD v5, 16 kHz) ------------------------------- */
+/* Defaults: threshold 0.5, min_speech_duration_ms 250, min_silence_duration_ms 100, max_speech_duration_s FLT_MAX,
+ * speech_pad_ms 30, samples_overlap 0.1; context: n_threads 4, use_gpu true, gpu_device 0. A probability covers 512
+ * samples (32 ms); the LSTM state starts at zero with every whisper_vad_detect_speech call. Segment times t0 / t1 are in
+ * 10 ms units, like every other time of this header, and so whisper-rs documents them (centiseconds); upstream releases
+ * have differed here (seconds in some), which cannot be checked offline. An init function returns NULL, with one line
+ * on stderr, for a file that is unreadable, truncated, of another geometry than v5 at 16 kHz, or that lacks, repeats or
+ * misshapes a tensor. */
+WHISPER_API struct whisper_vad_params         whisper_vad_default_params(void);
+WHISPER_API struct whisper_vad_context_params whisper_vad_default_context_params(void);
+WHISPER_API struct whisper_vad_context * whisper_vad_init_from_file_with_params(const char * path_model, struct whisper_vad_context_params params);
+WHISPER_API struct whisper_vad_context * whisper_vad_init_with_params(struct whisper_model_loader * loader, struct whisper_vad_context_params params);
+WHISPER_API bool    whisper_vad_detect_speech(struct whisper_vad_context * vctx, const float * samples, int n_samples);
+WHISPER_API int     whisper_vad_n_probs(struct whisper_vad_context * vctx);
+WHISPER_API float * whisper_vad_probs(struct whisper_vad_context * vctx);
+WHISPER_API struct whisper_vad_segments * whisper_vad_segments_from_probs(struct whisper_vad_context * vctx, struct whisper_vad_params params);
+WHISPER_API struct whisper_vad_segments * whisper_vad_segments_from_samples(struct whisper_vad_context * vctx, struct whisper_vad_params params, const float * samples, int n_samples);
+WHISPER_API int   whisper_vad_segments_n_segments(struct whisper_vad_segments * segments);
+WHISPER_API float whisper_vad_segments_get_segment_t0(struct whisper_vad_segments * segments, int i_segment);
+WHISPER_API float whisper_vad_segments_get_segment_t1(struct whisper_vad_segments * segments, int i_segment);
+WHISPER_API void  whisper_vad_free_segments(struct whisper_vad_segments * segments);
+WHISPER_API void  whisper_vad_free(struct whisper_vad_context * ctx);
 
 /* ---- benchmarks / logging -------------------------------------------------------------------- */
 WHISPER_API int whisper_bench_memcpy(int n_threads);

@@ -200,7 +200,9 @@ WHISPER_API int whisper_mi355x_set_audio_ctx(struct whisper_state * state, int a
  * (bytes), 9 / 10 / 11 the token-timestamp alignment's score (FLOPs), cost (bytes) and DTW (bytes) kernels,
  * 12 beam search's top-k logits kernel (bytes), 13 its self-cache gather (bytes read + written),
  * 14 the sampled draw of best_of candidates (bytes: two passes over the rows' probs),
- * 15 the token-time kernels (signal energy and the voice-activity adjust; bytes).
+ * 15 the token-time kernels (signal energy and the voice-activity adjust; bytes),
+ * 16 the grammar's reject kernel (bytes), 17 the three VAD kernels (whisper_full_params.vad; bytes). The bits of
+ * classes 16 and 17 lie in the layer-stride field below: time them with classes 2 and 3 off.
  * class_mask bit k times class k (0 = off); bits 16..23, when > 1, time
  * the decoder's per-layer attention launches (classes 2, 3) of every k-th layer only.
  * Every call resets the counters; stats out = {total ms, launches, total work}. */
@@ -218,6 +220,11 @@ WHISPER_API long whisper_mi355x_pdec_give_ups(struct whisper_state * state);
  * state since it was created (or recycled), the bytes whole-sequence copies would have been (no common-prefix
  * rule), 0}. Not reset by whisper_mi355x_kernel_timing. */
 #define WHISPER_MI355X_KSTAT_BEAM_GATHER 101
+/* Pseudo classes of whisper_mi355x_kernel_stats: class 17 (the VAD kernels) by kernel, out as for a class: vad_frontend,
+ * vad_lstm (with the head), vad_gather. Filled when class 17 is timed, reset with it. */
+#define WHISPER_MI355X_KSTAT_VAD_FRONTEND 102
+#define WHISPER_MI355X_KSTAT_VAD_LSTM 103
+#define WHISPER_MI355X_KSTAT_VAD_GATHER 104
 
 /* Kernel-level test/tuning hooks (device pointers): one fused-epilogue GEMM launch of the engine
  * (epi as in kernels.h: 0 store, 1 gelu, 2 residual f32, 4 f32, 5 cross K/V: out is then a cross cache of
@@ -457,6 +464,46 @@ WHISPER_API int whisper_mi355x_debug_logits_topk_gram(struct whisper_context * c
                                                       const int * rules, const float * temperature, int k, int split,
                                                       struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy,
                                                       const uint32_t * deny, const uint32_t * gram, float penalty);
+
+/* ---- whisper_full_params.vad and the whisper_vad_* block (kernels/vad.hip) ----
+ * With vad set, a call first filters its clips on the device: vad_frontend (one workgroup per clip and tile of four
+ * 512-sample windows: reflect pad, STFT, magnitude, four convs, the input half of the LSTM gates), vad_lstm (one workgroup
+ * of 512 threads per clip walks the clip's windows with W_hh in registers, then the head), one copy of the probabilities
+ * (4 bytes per 32 ms) to the host, get_speech_timestamps there, and vad_gather (the speech pieces end to end with 1600 zero
+ * samples between them). The rest of the call sees the filtered clips as device PCM. Segment k = samples [s_k, e_k) is
+ * copied as [s_k, min(e_k + samples_overlap * 16000, s_{k+1})) and the last as [s_k, e_k): the overlap is clamped to the
+ * next start, which keeps the time map monotone. The map takes a time t (10 ms units) of the filtered axis to the original
+ * one: inside piece k, orig_start_k + (160 t - vad_start_k); in the gap after piece k or beyond the last piece, the end of
+ * piece k; floor-divided by 160. It is applied once to every segment's t0 / t1 and to every token's t0, t1 and t_dtw that
+ * is not -1 (the new-segment callback sees mapped times too). whisper_mi355x_window_decisions' seek stays on the
+ * filtered axis. The three kernels are kernel-timing class 17 (K_VAD, work in bytes; WHISPER_MI355X_KSTAT_VAD_* gives it by kernel).
+ *
+ * whisper_mi355x_vad_ms: wall time of the filter step of the last full / full_batch call (the slower half of a paired
+ * batch); 0 with vad off. It is not one of whisper_mi355x_phase_ms' five slots.
+ * whisper_mi355x_vad_map: the piece table of a job of the last call, {orig_start, orig_end, vad_start, vad_end} in
+ * samples per piece, the first `cap` pieces into out[4 * cap]; returns the job's piece count (0 with vad off or no
+ * speech), -1 on bad arguments.
+ * whisper_mi355x_vad_probs_batch: the probabilities of n_clips clips in one pass (one launch of each kernel), host or
+ * device PCM; clip c's n_probs[c] = ceil(n_samples[c] / 512) values follow one another in probs_out (host). Every
+ * clip's values are those of a whisper_vad_detect_speech call on it alone, bit for bit. 0, or -1 on bad arguments.
+ * whisper_mi355x_debug_vad_frontend: the LSTM inputs xg[t] = W_ih x_t + b_ih + b_hh of one clip, host [n_windows][512];
+ * returns n_windows, -1 on bad arguments.
+ * whisper_mi355x_debug_vad_gather: vad_gather on caller data: host clips, clip c's n_pieces[c] pieces (four ints each,
+ * as above, one after the other in `pieces`), the filtered clips one after the other in out (host; clip c's length is
+ * its last piece's vad_end). Returns the samples written, -1 on bad arguments (a piece outside its clip, of different
+ * lengths on the two axes, or out of order included).
+ * All return -1 before touching the device. */
+struct whisper_vad_context;
+WHISPER_API double whisper_mi355x_vad_ms(struct whisper_state * state);
+WHISPER_API int whisper_mi355x_vad_map(struct whisper_state * state, int job, int * out, int cap);
+WHISPER_API int whisper_mi355x_vad_probs_batch(struct whisper_vad_context * vctx, const float * const * pcm,
+                                               const int * n_samples, int n_clips, bool pcm_on_device, float * probs_out,
+                                               int * n_probs);
+WHISPER_API int whisper_mi355x_debug_vad_frontend(struct whisper_vad_context * vctx, const float * pcm, int n_samples,
+                                                  float * xg_out);
+WHISPER_API int whisper_mi355x_debug_vad_gather(struct whisper_context * ctx, const float * const * pcm,
+                                                const int * n_samples, int n_clips, const int * pieces,
+                                                const int * n_pieces, float * out);
 
 /* Debug/tuning: the token-timestamp alignment kernels (kernels/align.hip) on caller data, one kernel each.
  * Clip k has n_rows[k] token rows and frames[k] = F_k frames; buffers hold the clips one after the other.

@@ -1,5 +1,6 @@
 // extern "C" whisper.h entry points (include/whisper.h) and the MI355X extensions
 // (include/whisper_mi355x.h). See include/whisper.h for the whisper.rs call site of each.
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -626,6 +627,7 @@ int whisper_mi355x_kernel_timing(struct whisper_state* s, int class_mask) {
     if (!s) return -1;
     s->ktime_mask = class_mask;
     for (auto& k : s->kstat) k = KStat();
+    for (auto& k : s->vad_kstat) k = KStat();
     return 0;
 }
 int whisper_mi355x_kernel_stats(struct whisper_state* s, int cls, double out[3]) {
@@ -641,6 +643,11 @@ int whisper_mi355x_kernel_stats(struct whisper_state* s, int cls, double out[3])
         out[0] = s->gather_rows * row_bytes;
         out[1] = s->gather_rows_full * row_bytes;
         out[2] = 0.0;
+        return 0;
+    }
+    if (s && cls >= WHISPER_MI355X_KSTAT_VAD_FRONTEND && cls <= WHISPER_MI355X_KSTAT_VAD_GATHER) {
+        const KStat& k = s->vad_kstat[cls - WHISPER_MI355X_KSTAT_VAD_FRONTEND];
+        out[0] = k.ms; out[1] = (double)k.count; out[2] = k.work;
         return 0;
     }
     if (!s || cls < 0 || cls >= K_NCLASS) return -1;
@@ -1405,6 +1412,201 @@ int whisper_mi355x_debug_align_dtw(struct whisper_context* ctx, const float* cos
         return 0;
     });
 }
+// ---- whisper.h's VAD block (Silero v5 on the device: vad.h) ------------------------------------------
+struct whisper_vad_context {
+    VadModel* m = nullptr;
+    VadScratch sc;
+    hipStream_t st = nullptr;
+    std::vector<float> probs;  // of the last whisper_vad_detect_speech
+    ~whisper_vad_context() {
+        if (m) hipSetDevice(m->device);
+        vad_scratch_free(sc);
+        if (st) hipStreamDestroy(st);
+        vad_model_free(m);
+    }
+};
+struct whisper_vad_segments {
+    std::vector<std::pair<float, float>> seg;  // 10 ms units
+};
+
+struct whisper_vad_params whisper_vad_default_params(void) {
+    whisper_vad_params p;
+    p.threshold = 0.5f;
+    p.min_speech_duration_ms = 250;
+    p.min_silence_duration_ms = 100;
+    p.max_speech_duration_s = FLT_MAX;
+    p.speech_pad_ms = 30;
+    p.samples_overlap = 0.1f;
+    return p;
+}
+struct whisper_vad_context_params whisper_vad_default_context_params(void) {
+    whisper_vad_context_params p;
+    p.n_threads = 4;
+    p.use_gpu = true;  // (the only path there is: false is accepted and ignored)
+    p.gpu_device = 0;
+    return p;
+}
+static whisper_vad_context* vad_ctx_from_image(const uint8_t* data, size_t size, int device, const char* what) {
+    whisper_vad_context* v = nullptr;
+    guarded(nullptr, [&]() -> int {
+        std::string err;
+        VadModel* m = vad_model_load(data, size, device, &err);
+        if (!m) {
+            fprintf(stderr, "whisper_mi355x: vad model '%s' refused: %s\n", what, err.c_str());
+            return -1;
+        }
+        v = new whisper_vad_context();
+        v->m = m;
+        try {
+            WM_CHECK(hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking));
+        } catch (...) {
+            delete v;
+            v = nullptr;
+            throw;
+        }
+        return 0;
+    });
+    return v;
+}
+struct whisper_vad_context* whisper_vad_init_from_file_with_params(const char* path_model, struct whisper_vad_context_params params) {
+    FILE* fp = path_model ? fopen(path_model, "rb") : nullptr;
+    if (!fp) {
+        fprintf(stderr, "whisper_mi355x: vad model '%s' refused: cannot open the file\n", path_model ? path_model : "(null)");
+        return nullptr;
+    }
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    size_t n;
+    while ((n = fread(chunk, 1, sizeof chunk, fp)) > 0 && buf.size() <= ((size_t)64 << 20)) buf.insert(buf.end(), chunk, chunk + n);
+    fclose(fp);
+    return vad_ctx_from_image(buf.data(), buf.size(), params.gpu_device, path_model);
+}
+struct whisper_vad_context* whisper_vad_init_with_params(struct whisper_model_loader* loader, struct whisper_vad_context_params params) {
+    if (!loader || !loader->read) return nullptr;
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    while (buf.size() <= ((size_t)64 << 20)) {  // (a VAD model is about 1 MB)
+        if (loader->eof && loader->eof(loader->context)) break;
+        const size_t n = loader->read(loader->context, chunk, sizeof chunk);
+        if (n == 0 || n > sizeof chunk) break;
+        buf.insert(buf.end(), chunk, chunk + n);
+    }
+    if (loader->close) loader->close(loader->context);
+    return vad_ctx_from_image(buf.data(), buf.size(), params.gpu_device, "(loader)");
+}
+bool whisper_vad_detect_speech(struct whisper_vad_context* vctx, const float* samples, int n_samples) {
+    if (!vctx || n_samples < 0 || (!samples && n_samples > 0)) return false;
+    return guarded(nullptr, [&]() -> int {
+        WM_CHECK(hipSetDevice(vctx->m->device));
+        std::vector<std::vector<float>> probs;
+        vad_probs_run(*vctx->m, vctx->sc, &samples, &n_samples, 1, false, vctx->st, nullptr, probs, nullptr);
+        vctx->probs.swap(probs[0]);
+        return 0;
+    }) == 0;
+}
+int whisper_vad_n_probs(struct whisper_vad_context* vctx) { return vctx ? (int)vctx->probs.size() : 0; }
+float* whisper_vad_probs(struct whisper_vad_context* vctx) { return vctx ? vctx->probs.data() : nullptr; }
+struct whisper_vad_segments* whisper_vad_segments_from_probs(struct whisper_vad_context* vctx, struct whisper_vad_params q) {
+    if (!vctx) return nullptr;
+    const VadParams vp{q.threshold, q.min_speech_duration_ms, q.min_silence_duration_ms, q.max_speech_duration_s, q.speech_pad_ms, q.samples_overlap};
+    whisper_vad_segments* out = new whisper_vad_segments();
+    for (const VadSpan& s : vad_segments_from_probs(vctx->probs.data(), (int)vctx->probs.size(), vp))
+        out->seg.push_back({(float)s.start / 160.0f, (float)s.end / 160.0f});
+    return out;
+}
+struct whisper_vad_segments* whisper_vad_segments_from_samples(struct whisper_vad_context* vctx, struct whisper_vad_params params,
+                                                               const float* samples, int n_samples) {
+    if (!whisper_vad_detect_speech(vctx, samples, n_samples)) return nullptr;
+    return whisper_vad_segments_from_probs(vctx, params);
+}
+int whisper_vad_segments_n_segments(struct whisper_vad_segments* segments) { return segments ? (int)segments->seg.size() : 0; }
+float whisper_vad_segments_get_segment_t0(struct whisper_vad_segments* segments, int i_segment) {
+    return segments && i_segment >= 0 && i_segment < (int)segments->seg.size() ? segments->seg[i_segment].first : 0.0f;
+}
+float whisper_vad_segments_get_segment_t1(struct whisper_vad_segments* segments, int i_segment) {
+    return segments && i_segment >= 0 && i_segment < (int)segments->seg.size() ? segments->seg[i_segment].second : 0.0f;
+}
+void whisper_vad_free_segments(struct whisper_vad_segments* segments) { delete segments; }
+void whisper_vad_free(struct whisper_vad_context* ctx) { delete ctx; }
+
+// ---- the VAD hooks of whisper_mi355x.h ------------------------------------------------------------------------------
+double whisper_mi355x_vad_ms(struct whisper_state* s) { return s ? s->vad_ms : 0.0; }
+int whisper_mi355x_vad_map(struct whisper_state* s, int job, int* out, int cap) {
+    if (!s || job < 0 || cap < 0 || (cap > 0 && !out)) return -1;
+    if (job >= (int)s->vad_maps.size()) return s->vad_maps.empty() && job < (int)s->results.size() ? 0 : -1;
+    const std::vector<VadPiece>& t = s->vad_maps[job];
+    for (int k = 0; k < (int)t.size() && k < cap; k++) {
+        out[4 * k] = t[k].orig_start; out[4 * k + 1] = t[k].orig_end; out[4 * k + 2] = t[k].vad_start; out[4 * k + 3] = t[k].vad_end;
+    }
+    return (int)t.size();
+}
+int whisper_mi355x_vad_probs_batch(struct whisper_vad_context* vctx, const float* const* pcm, const int* n_samples, int n_clips,
+                                   bool pcm_on_device, float* probs_out, int* n_probs) {
+    if (!vctx || !pcm || !n_samples || !probs_out || !n_probs || n_clips < 1 || n_clips > 65535) return -1;
+    for (int c = 0; c < n_clips; c++)
+        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) return -1;
+    return guarded(nullptr, [&]() -> int {
+        WM_CHECK(hipSetDevice(vctx->m->device));
+        std::vector<std::vector<float>> probs;
+        vad_probs_run(*vctx->m, vctx->sc, pcm, n_samples, n_clips, pcm_on_device, vctx->st, nullptr, probs, nullptr);
+        size_t at = 0;
+        for (int c = 0; c < n_clips; c++) {
+            n_probs[c] = (int)probs[c].size();
+            std::copy(probs[c].begin(), probs[c].end(), probs_out + at);
+            at += probs[c].size();
+        }
+        return 0;
+    });
+}
+int whisper_mi355x_debug_vad_frontend(struct whisper_vad_context* vctx, const float* pcm, int n_samples, float* xg_out) {
+    if (!vctx || n_samples < 0 || (n_samples > 0 && (!pcm || !xg_out))) return -1;
+    return guarded(nullptr, [&]() -> int {
+        WM_CHECK(hipSetDevice(vctx->m->device));
+        std::vector<std::vector<float>> probs;
+        vad_probs_run(*vctx->m, vctx->sc, &pcm, &n_samples, 1, false, vctx->st, nullptr, probs, xg_out);
+        return (int)probs[0].size();
+    });
+}
+int whisper_mi355x_debug_vad_gather(struct whisper_context* ctx, const float* const* pcm, const int* n_samples, int n_clips,
+                                    const int* pieces, const int* n_pieces, float* out) {
+    if (!ctx || !pcm || !n_samples || !pieces || !n_pieces || !out || n_clips < 1 || n_clips > 65535) return -1;
+    std::vector<std::vector<VadPiece>> tables(n_clips);
+    const int* q = pieces;
+    for (int c = 0; c < n_clips; c++) {
+        if (n_samples[c] < 0 || n_pieces[c] < 0 || (n_samples[c] > 0 && !pcm[c])) return -1;
+        int at = 0;  // every piece inside the clip, as long on both axes, and in order on the filtered one
+        for (int k = 0; k < n_pieces[c]; k++, q += 4) {
+            const VadPiece p{q[0], q[1], q[2], q[3]};
+            if (p.orig_start < 0 || p.orig_end <= p.orig_start || p.orig_end > n_samples[c] || p.vad_start < at ||
+                (long long)p.vad_end - p.vad_start != (long long)p.orig_end - p.orig_start)
+                return -1;
+            at = p.vad_end;
+            tables[c].push_back(p);
+        }
+    }
+    return guarded(nullptr, [&]() -> int {
+        WM_CHECK(hipSetDevice(ctx->c.device));
+        HookStream hs;
+        struct Sc { VadScratch sc; ~Sc() { vad_scratch_free(sc); } } h;
+        HookBufs b;
+        std::vector<const float*> dev(n_clips, nullptr);
+        for (int c = 0; c < n_clips; c++) {
+            float* d = (float*)b.get(std::max<size_t>((size_t)n_samples[c], 1) * sizeof(float));
+            if (n_samples[c] > 0) WM_CHECK(hipMemcpyAsync(d, pcm[c], (size_t)n_samples[c] * sizeof(float), hipMemcpyHostToDevice, hs.st));
+            dev[c] = d;
+        }
+        std::vector<const float*> optr;
+        std::vector<int> olen;
+        vad_gather_run(h.sc, dev.data(), tables, hs.st, nullptr, optr, olen);
+        size_t at = 0;
+        for (int c = 0; c < n_clips; c++) {
+            if (olen[c] > 0) WM_CHECK(hipMemcpy(out + at, optr[c], (size_t)olen[c] * sizeof(float), hipMemcpyDeviceToHost));
+            at += (size_t)olen[c];
+        }
+        return (int)at;
+    });
+}
+
 // ABI self-description (no device needed): sizes/offsets that a binding generator must agree on.
 int whisper_mi355x_abi_layout(size_t out[8]) {
     out[0] = sizeof(whisper_full_params);

@@ -7,6 +7,7 @@
 // the arithmetic is batched across clips: one encoder pass per group of windows, one cross-KV
 // GEMM, a ragged prefill, then lockstep decode steps over every clip still decoding. Per step the
 // host receives only a 32-byte TokOut per clip (plus the probs row of clips that sample at t>0).
+#include <optional>
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -71,6 +72,7 @@ struct KT {
     double work;
     hipStream_t st;
     hipEvent_t a = nullptr;
+    int sub = 0;  // (class K_VAD: the kernel)
     KT(whisper_state* s_, int c, double w, hipStream_t st_ = nullptr, bool on = true)
         : s(s_), cls(c), work(w), st(st_ ? st_ : s_->stream) {
         if (on && ((s->ktime_mask >> c) & 1)) { a = kt_event(s); kt_record(s, a, st); }
@@ -79,7 +81,7 @@ struct KT {
         if (!a) return;
         hipEvent_t b = kt_event(s);
         kt_record(s, b, st);
-        (s->capture_ev ? *s->capture_ev : s->kpending).push_back({cls, a, b, work});
+        (s->capture_ev ? *s->capture_ev : s->kpending).push_back({cls, a, b, work, sub});
     }
 };
 static void drop_graphs(whisper_state* s) {
@@ -115,6 +117,11 @@ void kt_flush(whisper_state* s) {
         s->kstat[p.cls].ms += ms;
         s->kstat[p.cls].work += p.cls == K_ATTN_SELF ? s->cur_self_work * p.work : p.work;
         s->kstat[p.cls].count++;
+        if (p.cls == K_VAD) {
+            s->vad_kstat[p.sub].ms += ms;
+            s->vad_kstat[p.sub].work += p.work;
+            s->vad_kstat[p.sub].count++;
+        }
         s->kpool.push_back(p.a);
         s->kpool.push_back(p.b);
     }
@@ -179,12 +186,15 @@ static void reset_for_reuse(whisper_state* s) {
     for (double& t : s->phase_ms) t = 0;
     s->align_ms = 0;
     s->tokts_ms = 0;
+    s->vad_ms = 0;
+    s->vad_maps.clear();
     s->align_info.clear();
     s->decoded_tokens = 0;
     s->last_enc_windows = 0;
     s->mel_ready = false;
     s->ktime_mask = 0;
     for (auto& k : s->kstat) k = KStat();
+    for (auto& k : s->vad_kstat) k = KStat();
     s->cur_self_work = 0;
     s->pdec_give_ups = 0;
     s->pdec_lost_ms = 0;
@@ -325,6 +335,7 @@ static void free_ws(Workspace& w) {
     dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans); dfree(w.deny); dfree(w.gram);
     if (w.h_gram) hipHostFree(w.h_gram);
     gram_dev_free(w.gd);
+    vad_scratch_free(w.vad);
     if (w.h_sslot) hipHostFree(w.h_sslot);
     if (w.h_sctr) hipHostFree(w.h_sctr);
     if (w.h_cand) hipHostFree(w.h_cand);
@@ -1576,7 +1587,12 @@ struct Sched {
     bool single_api;
     int n_max_steps;
     long decoded = 0;
-    double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0, t_tokts = 0;
+    double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0, t_tokts = 0, t_vad = 0;
+    // whisper_full_params.vad (vad_filter): the filtered clips on the device, their lengths, and per job the piece table
+    bool vad_on = false;
+    std::vector<const float*> vad_pcm;
+    std::vector<int> vad_n;
+    std::vector<std::vector<VadPiece>> vad_maps;
     // from pass to pass of full_batch_one: the call detects every clip's language (pass_lang); apply_audio_ctx has run;
     // a callback asked to stop; per row of the last prefill / decode step, a host-sampled row's probs
     bool need_lang = false, ctx_applied = false, aborted = false;
@@ -2867,7 +2883,9 @@ static void merge_twin(whisper_state* s, whisper_state* t, int n) {
         s->align_info.push_back(t->align_info[j]);  // (its cost matrix stays in the twin's workspace)
         s->beam_info.push_back(std::move(t->beam_info[j]));
         s->cand_info.push_back(std::move(t->cand_info[j]));
+        if (j < (int)t->vad_maps.size()) s->vad_maps.push_back(std::move(t->vad_maps[j]));
     }
+    s->vad_ms = std::max(s->vad_ms, t->vad_ms);
     s->align_ms = std::max(s->align_ms, t->align_ms);
     s->tokts_ms = std::max(s->tokts_ms, t->tokts_ms);
     s->decoded_tokens += t->decoded_tokens;
@@ -2881,6 +2899,12 @@ static void merge_twin(whisper_state* s, whisper_state* t, int n) {
         s->kstat[k].work += t->kstat[k].work;
         s->kstat[k].count += t->kstat[k].count;
         t->kstat[k] = KStat();
+    }
+    for (int k = 0; k < 3; k++) {
+        s->vad_kstat[k].ms += t->vad_kstat[k].ms;
+        s->vad_kstat[k].work += t->vad_kstat[k].work;
+        s->vad_kstat[k].count += t->vad_kstat[k].count;
+        t->vad_kstat[k] = KStat();
     }
 }
 
@@ -2967,7 +2991,7 @@ static int make_jobs(Sched& S, const int* n, int n_jobs) {
             std::rotate(j.prompt_past.begin(), j.prompt_past.end() - init_prompt_tokens.size(), j.prompt_past.end());
         }
         const bool no_audio = S.need_lang && 0 >= j.n_len_org;  // whisper_full_with_state: failed auto-detect -> -3
-        if (no_audio && S.single_api) return -3;
+        if (no_audio && S.single_api && !S.vad_on) return -3;  // (a clip the VAD found no speech in: no segments, 0)
         if (no_audio || j.seek_end < j.seek_start + 10) { j.phase = PH_DONE; continue; }
         j.lang_pending = S.need_lang;
         if (!S.need_lang) j.lang_id = lang_index(p.language);
@@ -3135,6 +3159,59 @@ static int pass_decode(Sched& S) {
     return 0;
 }
 
+// ---- whisper_full_params.vad: the Silero filter ahead of the mel (vad.h) --------------------------------
+std::shared_ptr<VadModel> vad_lookup(Context* c, const char* path) {
+    std::lock_guard<std::mutex> lk(c->vad_mu);
+    if (path && c->vad && c->vad_path == path) return c->vad;
+    std::string err;
+    VadModel* m = path ? vad_model_load_file(path, c->device, &err) : nullptr;
+    if (!m) {
+        fprintf(stderr, "whisper_mi355x: vad model '%s' refused: %s\n", path ? path : "(null)", path ? err.c_str() : "vad is set without vad_model_path");
+        return nullptr;  // (the cached model stays)
+    }
+    const int device = c->device;
+    c->vad = std::shared_ptr<VadModel>(m, [device](VadModel* q) { hipSetDevice(device); vad_model_free(q); });
+    c->vad_path = path;
+    return c->vad;
+}
+
+// a job's times from the filtered axis back to the original one: every segment's t0 / t1, and every token's t0, t1 and
+// t_dtw that is set
+static void vad_map_result(const std::vector<VadPiece>& map, std::vector<Segment>& segs) {
+    for (Segment& g : segs) {
+        g.t0 = vad_map_time(map, g.t0);
+        g.t1 = vad_map_time(map, g.t1);
+        for (TokenData& t : g.tokens) {
+            if (t.t0 != -1) t.t0 = vad_map_time(map, t.t0);
+            if (t.t1 != -1) t.t1 = vad_map_time(map, t.t1);
+            if (t.t_dtw != -1) t.t_dtw = vad_map_time(map, t.t_dtw);
+        }
+    }
+}
+
+// The filter step of a call with vad set: the probabilities of every job (frontend, lstm; one copy back), the segments
+// and piece tables on the host, the filtered PCM gathered on the device. After it the call reads S.vad_pcm / S.vad_n as
+// device clips. 0, or -11 when the model is refused.
+static int vad_filter(Sched& S, const float* const* pcm, const int* n, int n_jobs, bool on_device) {
+    ScopeTimer timed{S.t_vad};
+    const std::shared_ptr<VadModel> model = vad_lookup(S.c, S.p.vad_model_path);
+    if (!model) return -11;
+    whisper_state* s = S.s;
+    struct Timing { whisper_state* s; std::optional<KT> kt; } tm{s, std::nullopt};  // the launch in flight, timed as class K_VAD
+    const VadHooks hooks{[](void* u, int kernel, double bytes) { Timing* t = (Timing*)u; t->kt.emplace(t->s, K_VAD, bytes).sub = kernel; },
+                         [](void* u) { ((Timing*)u)->kt.reset(); }, &tm};
+    std::vector<std::vector<float>> probs;
+    vad_probs_run(*model, s->ws.vad, pcm, n, n_jobs, on_device, s->stream, &hooks, probs, nullptr);
+    const whisper_vad_params& q = S.p.vad_params;
+    const VadParams vp{q.threshold, q.min_speech_duration_ms, q.min_silence_duration_ms, q.max_speech_duration_s, q.speech_pad_ms, q.samples_overlap};
+    S.vad_maps.assign(n_jobs, {});
+    for (int j = 0; j < n_jobs; j++)
+        S.vad_maps[j] = vad_piece_table(vad_segments_from_probs(probs[j].data(), (int)probs[j].size(), vp), n[j], vp.samples_overlap);
+    vad_gather_run(s->ws.vad, s->ws.vad.dev_pcm.data(), S.vad_maps, s->stream, &hooks, S.vad_pcm, S.vad_n);
+    S.vad_on = true;
+    return 0;
+}
+
 // the windows that just finished with new segments: DTW alignment, then token_timestamps' t0 / t1 / vlen and max_len wrap
 static int pass_token_times(Sched& S) {
     if (S.c->dtw) align_windows(S);
@@ -3146,6 +3223,7 @@ static int pass_new_segment(Sched& S) {
     if (!S.single_api || !S.p.new_segment_callback || S.jobs[0].n_new_segments <= 0) return 0;
     Job& j = S.jobs[0];
     S.s->results[0] = j.result;
+    if (S.vad_on) vad_map_result(S.vad_maps[0], S.s->results[0]);
     S.p.new_segment_callback(S.c->owner, S.s, j.n_new_segments, S.p.new_segment_callback_user_data);
     j.n_new_segments = 0;
     return 0;
@@ -3156,6 +3234,7 @@ static void publish(Sched& S) {
     whisper_state* s = S.s;
     for (size_t k = 0; k < S.jobs.size(); k++) {
         s->results[k] = std::move(S.jobs[k].result);
+        if (S.vad_on) vad_map_result(S.vad_maps[k], s->results[k]);
         s->lang_ids[k] = S.jobs[k].lang_id;
         s->decisions[k] = std::move(S.jobs[k].decisions);
     }
@@ -3169,6 +3248,8 @@ static void publish(Sched& S) {
     s->phase_ms[0] = S.t_mel; s->phase_ms[1] = S.t_enc; s->phase_ms[2] = S.t_prefill; s->phase_ms[3] = S.t_decode; s->phase_ms[4] = S.t_logits;
     s->align_ms = S.t_align;
     s->tokts_ms = S.t_tokts;
+    s->vad_ms = S.t_vad;
+    s->vad_maps = std::move(S.vad_maps);
     std::lock_guard<std::mutex> lk(S.c->timings_mu);
     S.c->timings.encode_ms += (float)S.t_enc;
     S.c->timings.decode_ms += (float)S.t_decode;
@@ -3399,7 +3480,17 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     s->decisions.assign(n_jobs, {});
     s->align_info.assign(n_jobs, {});
     s->align_ms = s->tokts_ms = 0;
+    s->vad_ms = 0;
+    s->vad_maps.clear();
     s->decoded_tokens = 0;
+    // vad: the clips are filtered on the device first, and the call goes on with the filtered clips (a refused model
+    // ends the call before anything is encoded)
+    if (p.vad) {
+        if (const int r = vad_filter(S, pcm, n, n_jobs, on_device)) return r;
+        pcm = S.vad_pcm.data();
+        n = S.vad_n.data();
+        on_device = true;
+    }
     {
         ScopeTimer timed{S.t_mel};
         // beams of one clip share its cross K/V cache slot: beam_k > 1 runs in the cache form, with a self slot per beam
@@ -3441,6 +3532,7 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
         if (const int r = grammar_check(p, rules)) return r;
     }
     WM_CHECK(hipSetDevice(c->device));
+    if (p.vad && !vad_lookup(c, p.vad_model_path)) return -11;  // (one line, not one per half)
     if (!s->twin) s->twin = create_state(c);
     whisper_state* t = s->twin;
     t->ktime_mask = s->ktime_mask;

@@ -2,6 +2,7 @@
 // and the batched window scheduler that implements whisper_full semantics for many clips at once.
 #pragma once
 #include <map>
+#include <memory>
 #include <atomic>
 #include <mutex>
 #include <random>
@@ -14,6 +15,7 @@
 #include "common.h"
 #include "grammar.h"
 #include "kernels.h"
+#include "vad.h"
 
 namespace wm {
 
@@ -157,6 +159,12 @@ struct Context {
     // with it and freed with the context
     GramTable gram_tab{};
     void* gram_tab_mem[4] = {nullptr, nullptr, nullptr, nullptr};
+    // The VAD model of the last whisper_full_params.vad_model_path asked for (vad.h), keyed by the path
+    // (upstream keeps it per state). A call holds its own reference, so a call with another path on another thread
+    // replaces the entry without pulling the weights from under it.
+    std::mutex vad_mu;
+    std::string vad_path;
+    std::shared_ptr<VadModel> vad;
 };
 
 // The device side of a grammar call's masks (engine.cpp gram_masks): the call's flat rules, the rows' stack lists of a
@@ -291,12 +299,15 @@ struct Workspace {
     TtSeg* tt_segs = nullptr;
     TtSpan* tt_spans = nullptr;
     int tt_cap_clips = 0, tt_cap_segs = 0, tt_cap_spans = 0;
+    // whisper_full_params.vad (allocated by the first call that sets it): the PCM, the LSTM inputs, h and the
+    // probabilities of a call's clips, and the filtered PCM that compute_mel then reads
+    VadScratch vad;
 };
 
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
-              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_GRAMMAR, K_NCLASS };
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_GRAMMAR, K_VAD, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 // What a decode step does besides greedy's plain step (whisper_state::mode; all off between steps). topk > 0: the
@@ -339,6 +350,10 @@ struct whisper_state {
     double phase_ms[5] = {0, 0, 0, 0, 0};
     double align_ms = 0;  // token-timestamp alignment passes of the last call
     double tokts_ms = 0;  // token_timestamps passes (energy, phase 1, adjust, wrap) of the last call
+    // whisper_full_params.vad: the wall time of the filter step of the last call (0 when off), and per
+    // job the piece table that took its times back to the original axis (empty when off, or no speech)
+    double vad_ms = 0;
+    std::vector<std::vector<wm::VadPiece>> vad_maps;
     // per job of the last call: the cost matrix of its last aligned window (rows x frames f32 on the device,
     // in this state's or its twin's workspace); rows = 0: no window of the job was aligned
     struct AlignInfo { int rows = 0, frames = 0; const float* cost = nullptr; };
@@ -351,7 +366,8 @@ struct whisper_state {
     // kernel timing (off unless whisper_mi355x_kernel_timing enabled it)
     int ktime_mask = 0;  // bit k: time kernel class k
     wm::KStat kstat[wm::K_NCLASS];
-    struct KPending { int cls; hipEvent_t a, b; double work; };
+    wm::KStat vad_kstat[3];  // class K_VAD by kernel: frontend, lstm, gather (WHISPER_MI355X_KSTAT_VAD_*)
+    struct KPending { int cls; hipEvent_t a, b; double work; int sub = 0; };  // sub: which kernel of class K_VAD
     std::vector<KPending> kpending;
     std::vector<hipEvent_t> kpool;
     // decode steps replayed as hipGraphs, one per (active-clip count, timing mask, cross form, path
@@ -447,6 +463,9 @@ int deny_lookup(Context* c, bool suppress_nst, const char* regex, std::vector<ui
 // The call's grammar fields validated and flattened (grammar.h): 0 (rules off when the call has no grammar), or -9 and
 // one stderr line. Host only.
 int grammar_check(const whisper_full_params& p, GrammarRules& rules);
+// The context's VAD model for `path` (loaded on first use, or when the path changes): null and one stderr line when the
+// path is null or the file is unreadable or refused (whisper_full* then returns -11).
+std::shared_ptr<VadModel> vad_lookup(Context* c, const char* path);
 // the context's decoded vocabulary, built on first use
 const GramVocab& gram_vocab(Context* c);
 

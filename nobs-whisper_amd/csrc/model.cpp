@@ -501,6 +501,7 @@ bool load_context(Context* c, const char* path, int device, DType dt, bool load_
 }
 
 void free_context(Context* c) {
+    if (c && c->vad) { hipSetDevice(c->device); c->vad.reset(); c->vad_path.clear(); }
     if (c && c->arena) { hipSetDevice(c->device); hipFree(c->arena); c->arena = nullptr; }
     if (c && c->arena8) { hipSetDevice(c->device); hipFree(c->arena8); c->arena8 = nullptr; }
     if (c && c->arena_exp) { hipSetDevice(c->device); hipFree(c->arena_exp); c->arena_exp = nullptr; }

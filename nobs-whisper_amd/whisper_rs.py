@@ -63,6 +63,10 @@ class VadParams(C.Structure):
                 ("max_speech_duration_s", C.c_float), ("speech_pad_ms", C.c_int), ("samples_overlap", C.c_float)]
 
 
+class VadContextParams(C.Structure):
+    _fields_ = [("n_threads", C.c_int), ("use_gpu", C.c_bool), ("gpu_device", C.c_int)]
+
+
 class FullParams(C.Structure):
     """struct whisper_full_params (include/whisper.h), field for field."""
     _fields_ = [
@@ -109,6 +113,7 @@ class FullParams(C.Structure):
         self.grammar_penalty = penalty
 
 
+VAD_ERR = -11     # whisper_full* with vad set: vad_model_path is null, unreadable or refused (whisper.h)
 GRAMMAR_ERR = -9  # whisper_full*: the grammar is malformed or left-recursive (whisper.h)
 (GRETYPE_END, GRETYPE_ALT, GRETYPE_RULE_REF, GRETYPE_CHAR, GRETYPE_CHAR_NOT, GRETYPE_CHAR_RNG_UPPER,
  GRETYPE_CHAR_ALT) = range(7)
@@ -258,6 +263,24 @@ def lib() -> C.CDLL:
         "whisper_mi355x_align_ms": (C.c_double, [vp]),
         "whisper_mi355x_align_cost": (C.c_int, [vp, C.c_int, fp, C.c_long, ip, ip]),
         "whisper_mi355x_token_times_ms": (C.c_double, [vp]),
+        "whisper_vad_default_params": (VadParams, []),
+        "whisper_vad_default_context_params": (VadContextParams, []),
+        "whisper_vad_init_from_file_with_params": (vp, [C.c_char_p, VadContextParams]),
+        "whisper_vad_detect_speech": (C.c_bool, [vp, fp, C.c_int]),
+        "whisper_vad_n_probs": (C.c_int, [vp]),
+        "whisper_vad_probs": (fp, [vp]),
+        "whisper_vad_segments_from_probs": (vp, [vp, VadParams]),
+        "whisper_vad_segments_from_samples": (vp, [vp, VadParams, fp, C.c_int]),
+        "whisper_vad_segments_n_segments": (C.c_int, [vp]),
+        "whisper_vad_segments_get_segment_t0": (C.c_float, [vp, C.c_int]),
+        "whisper_vad_segments_get_segment_t1": (C.c_float, [vp, C.c_int]),
+        "whisper_vad_free_segments": (None, [vp]),
+        "whisper_vad_free": (None, [vp]),
+        "whisper_mi355x_vad_ms": (C.c_double, [vp]),
+        "whisper_mi355x_vad_map": (C.c_int, [vp, C.c_int, ip, C.c_int]),
+        "whisper_mi355x_vad_probs_batch": (C.c_int, [vp, C.POINTER(vp), ip, C.c_int, C.c_bool, fp, ip]),
+        "whisper_mi355x_debug_vad_frontend": (C.c_int, [vp, fp, C.c_int, fp]),
+        "whisper_mi355x_debug_vad_gather": (C.c_int, [vp, C.POINTER(vp), ip, C.c_int, ip, ip, fp]),
         "whisper_mi355x_debug_signal_energy": (C.c_int, [vp, fp, ip, C.c_int, fp]),
         "whisper_mi355x_debug_token_vad": (C.c_int, [vp, fp, ip, C.c_int, ip, ip, C.c_int, C.POINTER(TokenSpan)]),
         "whisper_mi355x_debug_align_scores": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, ip, ip, ip, C.c_int, ip, ip, vp]),
@@ -305,6 +328,91 @@ def lib() -> C.CDLL:
 
 
 # ---- whisper-rs shaped API ---------------------------------------------------------------------
+class VadContext:
+    """whisper-rs WhisperVadContext over whisper.h's whisper_vad_* block (Silero VAD v5 on the device)."""
+
+    def __init__(self, path: str, gpu_device: int = 0):
+        self.L = lib()
+        cp = self.L.whisper_vad_default_context_params()
+        cp.gpu_device = gpu_device
+        self.ptr = self.L.whisper_vad_init_from_file_with_params(path.encode(), cp)
+        if not self.ptr:
+            raise RuntimeError(f"whisper_vad_init_from_file_with_params({path}) failed")
+
+    def detect_speech(self, samples) -> bool:
+        import numpy as np
+        a = np.ascontiguousarray(samples, dtype=np.float32)
+        return bool(self.L.whisper_vad_detect_speech(self.ptr, a.ctypes.data_as(C.POINTER(C.c_float)), len(a)))
+
+    def probs(self):
+        import numpy as np
+        n = self.L.whisper_vad_n_probs(self.ptr)
+        return np.ctypeslib.as_array(self.L.whisper_vad_probs(self.ptr), shape=(n,)).copy() if n > 0 else np.zeros(0, np.float32)
+
+    def _take(self, segs) -> list:
+        if not segs:
+            raise RuntimeError("whisper_vad_segments_* failed")
+        L = self.L
+        out = [(L.whisper_vad_segments_get_segment_t0(segs, i), L.whisper_vad_segments_get_segment_t1(segs, i))
+               for i in range(L.whisper_vad_segments_n_segments(segs))]
+        L.whisper_vad_free_segments(segs)
+        return out
+
+    def segments_from_probs(self, params: VadParams | None = None) -> list:
+        """[(t0, t1)] in 10 ms units, from the probabilities of the last detect_speech"""
+        return self._take(self.L.whisper_vad_segments_from_probs(self.ptr, params or self.L.whisper_vad_default_params()))
+
+    def segments_from_samples(self, samples, params: VadParams | None = None) -> list:
+        import numpy as np
+        a = np.ascontiguousarray(samples, dtype=np.float32)
+        return self._take(self.L.whisper_vad_segments_from_samples(self.ptr, params or self.L.whisper_vad_default_params(),
+                                                                   a.ctypes.data_as(C.POINTER(C.c_float)), len(a)))
+
+    def probs_batch(self, clips, on_device: bool = False) -> list:
+        """whisper_mi355x_vad_probs_batch. clips: numpy arrays (host) or (device pointer, n_samples) pairs."""
+        import numpy as np
+        n = len(clips)
+        ptrs, lens, keep = (C.c_void_p * n)(), (C.c_int * n)(), []
+        for i, x in enumerate(clips):
+            if on_device:
+                ptrs[i], lens[i] = x[0], x[1]
+            else:
+                a = np.ascontiguousarray(x, dtype=np.float32)
+                keep.append(a)
+                ptrs[i], lens[i] = a.ctypes.data, len(a)
+        counts = [(lens[i] + 511) // 512 for i in range(n)]
+        out = np.zeros(max(sum(counts), 1), np.float32)
+        n_probs = (C.c_int * n)()
+        rc = self.L.whisper_mi355x_vad_probs_batch(self.ptr, ptrs, lens, n, on_device, out.ctypes.data_as(C.POINTER(C.c_float)), n_probs)
+        if rc != 0:
+            raise RuntimeError(f"whisper_mi355x_vad_probs_batch -> {rc}")
+        assert list(n_probs) == counts
+        cuts = np.cumsum([0] + counts)
+        return [out[cuts[i]:cuts[i + 1]].copy() for i in range(n)]
+
+    def debug_frontend(self, samples):
+        """whisper_mi355x_debug_vad_frontend: the LSTM inputs [n_windows][512] of one clip."""
+        import numpy as np
+        a = np.ascontiguousarray(samples, dtype=np.float32)
+        out = np.zeros(((len(a) + 511) // 512, 512), np.float32)
+        fp = C.POINTER(C.c_float)
+        rc = self.L.whisper_mi355x_debug_vad_frontend(self.ptr, a.ctypes.data_as(fp), len(a), out.ctypes.data_as(fp))
+        if rc != len(out):
+            raise RuntimeError(f"whisper_mi355x_debug_vad_frontend -> {rc}")
+        return out
+
+    def close(self):
+        if self.ptr:
+            self.L.whisper_vad_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class Segment:
     t0: int
@@ -478,6 +586,25 @@ class WhisperContext:
             return rc
         return [out[o:o + n].copy() for o, n in zip(off, ns)]
 
+    def debug_vad_gather(self, clips, tables):
+        """whisper_mi355x_debug_vad_gather: clips = numpy arrays, tables = per clip [(orig_start, orig_end, vad_start,
+        vad_end)]; returns the filtered clips, or the (negative) return code."""
+        import numpy as np
+        n = len(clips)
+        arrs = [np.ascontiguousarray(x, dtype=np.float32) for x in clips]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        lens = (C.c_int * n)(*[len(a) for a in arrs])
+        flat = [v for t in tables for p in t for v in p]
+        pieces = (C.c_int * max(len(flat), 1))(*flat)
+        n_pieces = (C.c_int * n)(*[len(t) for t in tables])
+        out_len = [t[-1][3] if t else 0 for t in tables]
+        out = np.zeros(max(sum(max(v, 0) for v in out_len), 1), np.float32)
+        rc = self.L.whisper_mi355x_debug_vad_gather(self.ptr, ptrs, lens, n, pieces, n_pieces, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if rc < 0:
+            return rc
+        cuts = np.cumsum([0] + out_len)
+        return [out[cuts[i]:cuts[i + 1]].copy() for i in range(n)]
+
     def debug_token_vad(self, energies, segs):
         """whisper_mi355x_debug_token_vad: energies = the clips' energy signals; segs = [(clip, [(t0, t1, is_text), ..])].
         One launch; the adjusted [(t0, t1), ..] per segment, or the negative return code."""
@@ -607,6 +734,27 @@ class WhisperState:
                                L.whisper_mi355x_batch_segment_t1(self.ptr, job, i),
                                L.whisper_mi355x_batch_segment_text(self.ptr, job, i), toks))
         return out
+
+    def vad_ms(self) -> float:
+        """whisper_mi355x_vad_ms: wall time of the VAD filter step of the last call (0 with vad off)."""
+        return float(self.L.whisper_mi355x_vad_ms(self.ptr))
+
+    def vad_kernel_stats(self) -> dict:
+        """Class 17 by kernel (WHISPER_MI355X_KSTAT_VAD_*): {kernel: (ms, launches, bytes)}; zeros unless class 17 is timed."""
+        out, res = (C.c_double * 3)(), {}
+        for k, name in enumerate(("frontend", "lstm", "gather")):
+            assert self.L.whisper_mi355x_kernel_stats(self.ptr, 102 + k, out) == 0
+            res[name] = (out[0], int(out[1]), out[2])
+        return res
+
+    def vad_map(self, job: int = 0) -> list:
+        """whisper_mi355x_vad_map: the job's piece table [(orig_start, orig_end, vad_start, vad_end)] in samples."""
+        n = self.L.whisper_mi355x_vad_map(self.ptr, job, None, 0)
+        if n < 0:
+            raise RuntimeError("whisper_mi355x_vad_map failed")
+        buf = (C.c_int * max(4 * n, 1))()
+        self.L.whisper_mi355x_vad_map(self.ptr, job, buf, n)
+        return [tuple(buf[4 * k:4 * k + 4]) for k in range(n)]
 
     def grammar_stats(self) -> dict:
         """whisper_mi355x_grammar_stats: rows of grammar calls decided by the reject kernel, patched by the host after the
