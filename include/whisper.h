@@ -61,6 +61,11 @@
  * convert-silero-vad-to-ggml.py writes it, restated in tools/make_vad_model.py; like the struct layouts, that layout
  * could not be checked against a real file offline.
  *
+ * whisper_full_parallel is implemented (whisper_mi355x.h): the recording is cut into n_processors pieces
+ * where upstream cuts it, the pieces are decoded side by side as one device batch on the default state (no threads, no
+ * extra states), and their segments are merged with upstream's time shift. Unlike upstream, token times are shifted with
+ * their segments. n_processors <= 1 is whisper_full; n_processors > 128 returns -1.
+ *
  * Still accepted and ignored: tdrz_enable.
  */
 #ifndef WHISPER_H

@@ -130,6 +130,32 @@ struct whisper_mi355x_window_decision {
 WHISPER_API int whisper_mi355x_window_decisions(struct whisper_state * state, int job,
                                                 struct whisper_mi355x_window_decision * out, int cap);
 
+/* whisper_full_parallel as one device batch. The recording is cut as upstream cuts it: with
+ * offset_samples = 16000 * offset_ms / 1000 and n_per = (n_samples - offset_samples) / n_processors (int arithmetic),
+ * piece 0 is [0, offset_samples + n_per) with the caller's params, piece k >= 1 starts at cut_k = offset_samples +
+ * k * n_per with offset_ms = 0 and no new-segment or progress callback, and the last piece runs to n_samples;
+ * duration_ms, encoder_begin_callback and abort_callback hold for every piece. The pieces are the jobs of one batch on
+ * `state` (beam search with n_processors * beam_size > 32: consecutive groups of 32 / beam_size jobs): piece 0 is decoded
+ * as whisper_full_with_state on `state` decodes it (carried prompt, rng, language, live callbacks), every other piece
+ * as on a fresh state. The results are merged in piece order into what the whisper_full_*_from_state getters of `state`
+ * see: a segment of piece k >= 1 gains 100 * (cut_k - offset_samples) / 16000 + offset_ms / 10 on t0 and t1, then t0 =
+ * max(t0, t1 of the segment before it), and new_segment_callback is called with n_new = 1 after each one. Unlike
+ * upstream, which leaves them relative to the piece, every token t0 / t1 / t_dtw that is not -1 gains the same amount
+ * (unclamped). whisper_mi355x_window_decisions(state, 0, ..) gives the pieces' records in piece order, seek shifted
+ * alike. n_processors <= 1 (or n_per <= 0) is whisper_full_with_state; n_processors > 128 returns -1 (one stderr line).
+ * A group's error code is returned at once.
+ * snap_ms > 0 moves every interior cut to the quietest 20 ms near it: of the 320-sample windows w that lie wholly
+ * inside the recording with |320 w - cut_k| <= 16 * snap, snap = min(snap_ms, 1000 * (n_per / 2 - 320) / 16000) (not
+ * positive: nothing moves), the one with the lowest RMS (the device pass of whisper_mi355x_find_silence_boundaries;
+ * ties: the smaller |320 w - cut_k|, then the smaller w) gives the new cut 320 w + 160. Piece lengths and time shifts
+ * follow the moved cuts. whisper_full_parallel is this call with the default state, snap_ms = 0 and host PCM.
+ * whisper_mi355x_parallel_cuts: the piece starts (samples; cuts[0] = 0) of the last such call on the state; returns
+ * their count (at most cap are copied). */
+WHISPER_API int whisper_mi355x_full_parallel(struct whisper_context * ctx, struct whisper_state * state,
+                                             struct whisper_full_params params, const float * pcm, int n_samples,
+                                             int n_processors, int snap_ms, bool pcm_on_device);
+WHISPER_API int whisper_mi355x_parallel_cuts(struct whisper_state * state, int * cuts, int cap);
+
 /* Phase timings of the last full/full_batch call, milliseconds (host wall clock around
  * stream-synchronised phases): mel, encode (incl. cross-KV), prefill, decode steps, logits. */
 WHISPER_API int whisper_mi355x_phase_ms(struct whisper_state * state, double out[5]);

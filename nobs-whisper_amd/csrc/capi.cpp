@@ -390,8 +390,23 @@ int whisper_full_with_state(struct whisper_context* ctx, struct whisper_state* s
 int whisper_full(struct whisper_context* ctx, struct whisper_full_params p, const float* samples, int n) {
     return whisper_full_with_state(ctx, ctx ? ctx->c.default_state : nullptr, p, samples, n);
 }
-int whisper_full_parallel(struct whisper_context* ctx, struct whisper_full_params p, const float* samples, int n, int) {
-    return whisper_full(ctx, p, samples, n);
+// the pieces of the recording as the jobs of one device batch, merged on the recording's axis
+int whisper_mi355x_full_parallel(struct whisper_context* ctx, struct whisper_state* s, struct whisper_full_params p,
+                                 const float* pcm, int n_samples, int n_processors, int snap_ms, bool pcm_on_device) {
+    if (n_processors > kParallelMax) {  // the clips of one scheduler (asked before anything else: no device is needed)
+        fprintf(stderr, "whisper_mi355x: whisper_full_parallel: n_processors %d > %d\n", n_processors, kParallelMax);
+        return -1;
+    }
+    if (!ctx || !s || n_samples < 0 || (!pcm && n_samples > 0)) return -1;
+    return guarded(s, [&] { return full_parallel(&ctx->c, s, p, pcm, n_samples, n_processors, snap_ms, pcm_on_device); });
+}
+int whisper_mi355x_parallel_cuts(struct whisper_state* s, int* cuts, int cap) {
+    if (!s) return 0;
+    for (int k = 0; cuts && k < cap && k < (int)s->par_cuts.size(); k++) cuts[k] = s->par_cuts[k];
+    return (int)s->par_cuts.size();
+}
+int whisper_full_parallel(struct whisper_context* ctx, struct whisper_full_params p, const float* samples, int n, int n_processors) {
+    return whisper_mi355x_full_parallel(ctx, ctx ? ctx->c.default_state : nullptr, p, samples, n, n_processors, 0, false);
 }
 
 static const Segment* seg(whisper_state* s, int job, int i) {

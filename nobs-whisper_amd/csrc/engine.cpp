@@ -1529,6 +1529,9 @@ struct Seq {
 
 struct Job {
     int slot = 0;
+    // the single API's job (job 0 of a call with Sched::single_api): the state's carried prompt and rng, the progress and
+    // new-segment callbacks, -3 without audio. Every other job decodes as on a fresh state.
+    bool single = false;
     int n_samples = 0, n_len = 0, n_len_org = 0;
     int seek = 0, seek_start = 0, seek_end = 0;
     bool lang_pending = false;
@@ -1584,7 +1587,7 @@ struct Sched {
     FullOpts o;
     std::vector<float> temps;
     std::vector<Job> jobs;
-    bool single_api;
+    bool single_api;  // job 0 is the single API's job (Job::single); no other job is
     int n_max_steps;
     long decoded = 0;
     double t_mel = 0, t_enc = 0, t_prefill = 0, t_decode = 0, t_logits = 0, t_align = 0, t_tokts = 0, t_vad = 0;
@@ -2977,21 +2980,22 @@ static int make_jobs(Sched& S, const int* n, int n_jobs) {
     for (int k = 0; k < n_jobs; k++) {
         Job& j = S.jobs[k];
         j.slot = k;
+        j.single = S.single_api && k == 0;
         j.n_samples = n[k];
         j.n_len = mel_n_len(n[k]);
         j.n_len_org = mel_n_len_org(n[k]);
-        j.seek_start = p.offset_ms / 10;
+        j.seek_start = S.o.pieces && !j.single ? 0 : p.offset_ms / 10;  // (a later piece of a recording: offset_ms = 0)
         j.seek_end = p.duration_ms == 0 ? j.n_len_org : j.seek_start + p.duration_ms / 10;
         j.seek = j.seek_start;
-        j.rng = S.single_api ? &S.s->rng : &j.own_rng;
-        if (S.single_api) j.prompt_past = S.s->prompt_past;
+        j.rng = j.single ? &S.s->rng : &j.own_rng;
+        if (j.single) j.prompt_past = S.s->prompt_past;
         if (p.no_context) j.prompt_past.clear();
         if (!init_prompt_tokens.empty()) {
             for (int t : init_prompt_tokens) j.prompt_past.push_back(t);
             std::rotate(j.prompt_past.begin(), j.prompt_past.end() - init_prompt_tokens.size(), j.prompt_past.end());
         }
         const bool no_audio = S.need_lang && 0 >= j.n_len_org;  // whisper_full_with_state: failed auto-detect -> -3
-        if (no_audio && S.single_api && !S.vad_on) return -3;  // (a clip the VAD found no speech in: no segments, 0)
+        if (no_audio && j.single && !S.vad_on) return -3;  // (a clip the VAD found no speech in: no segments, 0)
         if (no_audio || j.seek_end < j.seek_start + 10) { j.phase = PH_DONE; continue; }
         j.lang_pending = S.need_lang;
         if (!S.need_lang) j.lang_id = lang_index(p.language);
@@ -3013,12 +3017,12 @@ static int pass_encode(Sched& S) {
     for (int k = 0; k < (int)S.jobs.size(); k++) {
         Job& j = S.jobs[k];
         if (j.phase != PH_ENCODE) continue;
-        if (S.single_api && p.progress_callback) {
+        if (j.single && p.progress_callback) {
             const int prog = (100 * (j.seek - j.seek_start)) / std::max(1, j.seek_end - j.seek_start);
             p.progress_callback(S.c->owner, S.s, prog, p.progress_callback_user_data);
         }
         if (j.seek + 10 >= j.seek_end && !j.lang_pending) { j.phase = PH_DONE; continue; }
-        if ((S.single_api && p.encoder_begin_callback && !p.encoder_begin_callback(S.c->owner, S.s, p.encoder_begin_callback_user_data)) ||
+        if (((S.single_api || S.o.pieces) && p.encoder_begin_callback && !p.encoder_begin_callback(S.c->owner, S.s, p.encoder_begin_callback_user_data)) ||
             abort_asked(S)) {
             S.aborted = true;
             return 0;
@@ -3517,7 +3521,136 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
             if ((rc = pass(S)) != 0 || S.aborted) break;
     if (rc) return rc;
     if (const int r = apply_audio_ctx(S)) return r;  // (if no pass did: no clip had a window to encode, or a stop came first)
+    if (o.stopped) *o.stopped = S.aborted;
     publish(S);
+    return 0;
+}
+
+// ---- whisper_full_parallel (parallel.h) ------------------------------------------------------------------
+// The cuts moved to the quietest 20 ms near them: the RMS of the candidate windows of every interior cut comes from the
+// device pass of whisper_mi355x_find_silence_boundaries, one short clip per cut (a window's RMS does not depend on the
+// windows around it, so only the candidates' samples are read, and from host PCM only they are uploaded), and 4 bytes per
+// window come back; the choice is the host's (parallel_snap_pick).
+static int snap_cuts(Context* c, const float* pcm, int n_samples, bool on_device, int snap, std::vector<int>& cuts) {
+    const int nc = (int)cuts.size() - 1;
+    std::vector<SnapRange> rg(nc);
+    std::vector<const float*> ptr(nc);
+    std::vector<int> len(nc), counts(nc);
+    int stride = 1;
+    for (int k = 0; k < nc; k++) {
+        rg[k] = parallel_snap_range(n_samples, cuts[k + 1], snap);
+        ptr[k] = pcm + (size_t)rg[k].w_lo * kParWindow;
+        len[k] = rg[k].n_w * kParWindow;
+        stride = std::max(stride, rg[k].n_w);
+    }
+    std::vector<float> rms((size_t)nc * stride);
+    if (whisper_mi355x_find_silence_boundaries(c->device, ptr.data(), len.data(), nc, kParRate, on_device, counts.data(), nullptr, 0,
+                                               nullptr, rms.data(), stride) != 0)
+        return WHISPER_MI355X_ERR_RUNTIME;
+    for (int k = 0; k < nc; k++) cuts[k + 1] = parallel_snap_pick(rms.data() + (size_t)k * stride, rg[k], cuts[k + 1]);
+    return 0;
+}
+
+int full_parallel(Context* c, whisper_state* s, const whisper_full_params& p, const float* pcm, int n_samples,
+                  int n_processors, int snap_ms, bool on_device) {
+    if (n_processors > kParallelMax) return -1;  // (capi.cpp has said why)
+    const int n_per = n_processors > 1 ? parallel_n_per(n_samples, p.offset_ms, n_processors) : 0;
+    if (n_processors <= 1 || n_per <= 0) {  // whisper_full (also when offset_ms leaves less than a sample per piece)
+        s->par_cuts.assign(1, 0);
+        return full_batch(c, s, p, &pcm, &n_samples, 1, on_device, FullOpts(), true);
+    }
+    WM_CHECK(hipSetDevice(c->device));
+    std::vector<int> cuts = parallel_cuts(n_samples, p.offset_ms, n_processors);
+    if (const int snap = parallel_snap(snap_ms, n_per); snap > 0)
+        if (const int r = snap_cuts(c, pcm, n_samples, on_device, snap, cuts)) return r;
+    std::vector<const float*> ptr(n_processors);
+    std::vector<int> len(n_processors);
+    for (int k = 0; k < n_processors; k++) {
+        ptr[k] = pcm + cuts[k];
+        len[k] = (k + 1 < n_processors ? cuts[k + 1] : n_samples) - cuts[k];
+    }
+    // beam search: every beam is a decoder row, so the pieces run in consecutive groups of 32 / beam_size jobs; the
+    // single API's job exists in the first group only. (An error of a group ends the call: the state's carried prompt and
+    // language are put back, and nothing of the call stays in the state.)
+    const int beam_k = p.strategy == WHISPER_SAMPLING_BEAM_SEARCH ? std::max(1, p.beam_search.beam_size) : 1;
+    const int group = beam_k > 1 && beam_k <= kBeamMax ? std::max(1, kBeamMaxRows / beam_k) : n_processors;
+    const std::vector<int> past0 = s->prompt_past;
+    const int lang0 = s->lang_id;
+    std::vector<std::vector<Segment>> results(n_processors);
+    std::vector<std::vector<whisper_mi355x_window_decision>> decisions(n_processors);
+    whisper_state::AlignInfo align0;
+    std::vector<whisper_state::BeamRec> beam0, cand0;
+    std::vector<VadPiece> vad0;
+    int lang_job0 = 0;
+    double phase_ms[5] = {0, 0, 0, 0, 0}, align_ms = 0, tokts_ms = 0, vad_ms = 0;
+    long decoded = 0;
+    bool stopped = false;
+    const auto undo = [&] {
+        s->prompt_past = past0;
+        s->lang_id = lang0;
+        s->results.clear();
+        s->decisions.clear();
+    };
+    for (int a = 0; a < n_processors && !stopped; a += group) {
+        const int nj = std::min(group, n_processors - a);
+        FullOpts o;
+        o.pieces = true;
+        o.stopped = &stopped;
+        int rc = 0;
+        try {
+            rc = full_batch_one(c, s, p, ptr.data() + a, len.data() + a, nj, on_device, o, a == 0);
+        } catch (...) {
+            undo();
+            throw;
+        }
+        if (rc) {
+            undo();
+            return rc;
+        }
+        for (int j = 0; j < nj; j++) {
+            results[a + j] = std::move(s->results[j]);
+            decisions[a + j] = std::move(s->decisions[j]);
+        }
+        if (a == 0) {
+            lang_job0 = s->lang_ids[0];
+            if (nj == n_processors) align0 = s->align_info[0];  // (a later group's alignment would overwrite its cost matrix)
+            beam0 = std::move(s->beam_info[0]);
+            cand0 = std::move(s->cand_info[0]);
+            if (!s->vad_maps.empty()) vad0 = std::move(s->vad_maps[0]);
+        }
+        for (int k = 0; k < 5; k++) phase_ms[k] += s->phase_ms[k];
+        align_ms += s->align_ms;
+        tokts_ms += s->tokts_ms;
+        vad_ms += s->vad_ms;
+        decoded += s->decoded_tokens;
+    }
+    // The merge, in piece order, into results[0]: the only thing the whisper_full_* getters see. Piece 0's times are
+    // absolute already (its offset_ms was in force, and its new-segment callback ran while it was decoded).
+    s->results.assign(1, std::move(results[0]));
+    s->decisions.assign(1, std::move(decisions[0]));
+    s->lang_ids.assign(1, lang_job0);
+    s->align_info.assign(1, align0);
+    s->beam_info.assign(1, std::move(beam0));
+    s->cand_info.assign(1, std::move(cand0));
+    s->vad_maps.clear();
+    if (p.vad) s->vad_maps.push_back(std::move(vad0));
+    for (int k = 0; k < 5; k++) s->phase_ms[k] = phase_ms[k];
+    s->align_ms = align_ms;
+    s->tokts_ms = tokts_ms;
+    s->vad_ms = vad_ms;
+    s->decoded_tokens = decoded;
+    std::vector<Segment>& out = s->results[0];
+    for (int k = 1; k < n_processors; k++) {
+        const int64_t shift = parallel_shift(cuts[k], p.offset_ms);
+        parallel_merge_piece(out, results[k], shift, [&] {
+            if (p.new_segment_callback) p.new_segment_callback(c->owner, s, 1, p.new_segment_callback_user_data);
+        });
+        for (whisper_mi355x_window_decision d : decisions[k]) {
+            d.seek += (int)shift;
+            s->decisions[0].push_back(d);
+        }
+    }
+    s->par_cuts = cuts;
     return 0;
 }
 

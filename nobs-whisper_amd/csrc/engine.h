@@ -15,6 +15,7 @@
 #include "common.h"
 #include "grammar.h"
 #include "kernels.h"
+#include "parallel.h"
 #include "vad.h"
 
 namespace wm {
@@ -354,6 +355,8 @@ struct whisper_state {
     // job the piece table that took its times back to the original axis (empty when off, or no speech)
     double vad_ms = 0;
     std::vector<std::vector<wm::VadPiece>> vad_maps;
+    // the piece starts (samples) of the last whisper_full_parallel call on this state (whisper_mi355x_parallel_cuts)
+    std::vector<int> par_cuts;
     // per job of the last call: the cost matrix of its last aligned window (rows x frames f32 on the device,
     // in this state's or its twin's workspace); rows = 0: no window of the job was aligned
     struct AlignInfo { int rows = 0, frames = 0; const float* cost = nullptr; };
@@ -450,13 +453,24 @@ struct FullOpts {
     const int* spot = nullptr;
     int n_spot = 0;
     float* spot_logits = nullptr;
+    // whisper_full_parallel (full_parallel below): the jobs are the pieces of one recording. Every job but
+    // the single API's (job 0 of a call with single_api) decodes from its own time 0 (offset_ms = 0), and
+    // encoder_begin_callback is asked for every job. stopped (if given): set when a callback ended the call early.
+    bool pieces = false;
+    bool* stopped = nullptr;
 };
-// whisper_full over n_jobs clips. B=1 with the state's own prompt_past/rng reproduces
-// whisper_full_with_state; B>1 treats every clip as a fresh state.
+// whisper_full over n_jobs clips. With single_api, job 0 is the single API's job: it runs on the state's own
+// prompt_past / rng and has the new-segment and progress callbacks (one clip: whisper_full_with_state); every other clip
+// is decoded as on a fresh state.
 // tokens decoded by every whisper_full / full_batch call of the process (whisper_mi355x_decoded_tokens_total)
 extern std::atomic<long> g_decoded_tokens_total;
 int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const float* const* pcm, const int* n,
                int n_jobs, bool on_device, const FullOpts& o, bool single_api);
+// whisper_full_parallel / whisper_mi355x_full_parallel: the recording cut into n_processors pieces
+// (parallel.h; snap_ms > 0 moves each cut to the quietest 20 ms near it), the pieces decoded as the jobs of one scheduler
+// (beam search: in groups of 32 / beam_size), their results merged into results[0] of the state on the recording's axis.
+int full_parallel(Context* c, whisper_state* s, const whisper_full_params& p, const float* pcm, int n_samples,
+                  int n_processors, int snap_ms, bool on_device);
 // The deny mask of (suppress_nst, regex) from the context's one-entry cache, built when the key differs: 0 and the
 // words in `words` (if given), or -8 and one stderr line when the pattern does not compile. Host only.
 int deny_lookup(Context* c, bool suppress_nst, const char* regex, std::vector<uint32_t>* words);

@@ -192,6 +192,14 @@ def lib() -> C.CDLL:
         "whisper_free": (None, [vp]),
         "whisper_free_state": (None, [vp]),
         "whisper_full_with_state": (C.c_int, [vp, vp, FullParams, fp, C.c_int]),
+        "whisper_init_from_file_with_params": (vp, [C.c_char_p, WhisperContextParams]),
+        "whisper_full_parallel": (C.c_int, [vp, FullParams, fp, C.c_int, C.c_int]),
+        "whisper_full_n_segments": (C.c_int, [vp]),
+        "whisper_full_get_segment_text": (C.c_char_p, [vp, C.c_int]),
+        "whisper_full_get_segment_t0": (C.c_int64, [vp, C.c_int]),
+        "whisper_full_get_segment_t1": (C.c_int64, [vp, C.c_int]),
+        "whisper_mi355x_full_parallel": (C.c_int, [vp, vp, FullParams, vp, C.c_int, C.c_int, C.c_int, C.c_bool]),
+        "whisper_mi355x_parallel_cuts": (C.c_int, [vp, ip, C.c_int]),
         "whisper_full_n_segments_from_state": (C.c_int, [vp]),
         "whisper_full_get_segment_text_from_state": (C.c_char_p, [vp, C.c_int]),
         "whisper_full_get_segment_t0_from_state": (C.c_int64, [vp, C.c_int]),
@@ -496,6 +504,33 @@ class WhisperContext:
             raise RuntimeError(f"failed to load {path}")
         return self
 
+    @classmethod
+    def new_with_default_state(cls, path: str):
+        """whisper_init_from_file_with_params: a context with whisper.h's default state, the one whisper_full and
+        whisper_full_parallel work on (f16 unless WHISPER_MI355X_DTYPE says bf16)."""
+        self = cls.__new__(cls)
+        L = lib()
+        cp = L.whisper_context_default_params()
+        self.L = L
+        self.gpu_device = cp.gpu_device
+        self._states = weakref.WeakSet()
+        self.ptr = L.whisper_init_from_file_with_params(path.encode(), cp)
+        if not self.ptr:
+            raise RuntimeError(f"failed to load {path}")
+        return self
+
+    def full_parallel(self, params: FullParams, audio, n_processors: int) -> int:
+        """whisper_full_parallel on the default state (new_with_default_state)."""
+        import numpy as np
+        a = np.ascontiguousarray(audio, dtype=np.float32)
+        return self.L.whisper_full_parallel(self.ptr, params, a.ctypes.data_as(C.POINTER(C.c_float)), len(a), n_processors)
+
+    def default_segments(self) -> list:
+        """The default state's segments through whisper_full_n_segments / whisper_full_get_segment_*: (t0, t1, text)."""
+        L = self.L
+        return [(L.whisper_full_get_segment_t0(self.ptr, i), L.whisper_full_get_segment_t1(self.ptr, i),
+                 L.whisper_full_get_segment_text(self.ptr, i)) for i in range(L.whisper_full_n_segments(self.ptr))]
+
     def create_state(self) -> "WhisperState":
         return WhisperState(self)
 
@@ -662,6 +697,29 @@ class WhisperState:
         a = np.ascontiguousarray(audio, dtype=np.float32)
         return self.L.whisper_full_with_state(self.ctx.ptr, self.ptr, params,
                                               a.ctypes.data_as(C.POINTER(C.c_float)), len(a))
+
+    def full_parallel(self, params: FullParams, audio, n_processors: int) -> int:
+        """whisper-rs WhisperState::full_parallel: the recording cut into n_processors pieces where whisper.cpp cuts it, decoded
+        as one device batch on this state and merged. whisper_full_parallel is this on the default state."""
+        return self.mi355x_full_parallel(params, audio, n_processors, 0)
+
+    def mi355x_full_parallel(self, params: FullParams, audio, n_processors: int, snap_ms: int = 0, on_device: bool = False) -> int:
+        """whisper_mi355x_full_parallel: snap_ms > 0 moves each cut to the quietest 20 ms within snap_ms of it. audio: a numpy
+        array (host), or with on_device a (device pointer, n_samples) pair."""
+        import numpy as np
+        if on_device:
+            ptr, n = audio
+        else:
+            a = np.ascontiguousarray(audio, dtype=np.float32)
+            ptr, n = a.ctypes.data, len(a)
+        return self.L.whisper_mi355x_full_parallel(self.ctx.ptr, self.ptr, params, ptr, n, n_processors, snap_ms, on_device)
+
+    def parallel_cuts(self) -> list:
+        """whisper_mi355x_parallel_cuts: the piece starts (samples) of the last full_parallel call on this state."""
+        n = self.L.whisper_mi355x_parallel_cuts(self.ptr, None, 0)
+        buf = (C.c_int * max(n, 1))()
+        self.L.whisper_mi355x_parallel_cuts(self.ptr, buf, n)
+        return list(buf[:n])
 
     def full_n_segments(self) -> int:
         return self.L.whisper_full_n_segments_from_state(self.ptr)
