@@ -66,7 +66,36 @@
  * extra states), and their segments are merged with upstream's time shift. Unlike upstream, token times are shifted with
  * their segments. n_processors <= 1 is whisper_full; n_processors > 128 returns -1.
  *
- * Still accepted and ignored: tdrz_enable.
+ * whisper_full_params.logits_filter_callback is implemented (whisper_mi355x.h; whisper-rs
+ * FullParams::set_filter_logits_callback). It is called as cb(ctx, state, tokens, n_tokens, logits, user_data) once per
+ * decoder row per logits evaluation of whisper_full*, whisper_full_parallel and whisper_mi355x_full_batch* (greedy
+ * decoders, every beam, every best_of candidate, fixed-work and forced runs; not from whisper_decode* or
+ * whisper_lang_auto_detect*), on the calling thread, between two launches, with the state's stream drained; within a step
+ * the rows are called in the order they were staged. ctx and state are those of the call. This engine's contract:
+ *   - logits: n_vocab floats in host memory, valid during the call, any entry may be written (finite or -inf; not
+ *     checked). Already applied: the temperature divide (in float, when t > 0), suppress_blank on the initial step (EOT and
+ *     " "), <|notimestamps|>, no_timestamps, sot / nosp / solm (see tdrz_enable) / translate / transcribe / prev and the
+ *     language tokens; every entry those rules did not touch is the raw logit bit for bit (divided when t > 0). They are
+ *     not applied a second time: a callback that sets logits[sot] = 0 re-enables it, as upstream would.
+ *   - applied after it, to the row as the callback left it: the deny mask of suppress_nst / suppress_regex, suppress_eot
+ *     (fixed-work mode), timestamp pairing, max_initial_ts, monotonic timestamps, the log-softmax, the timestamp-mass
+ *     rule, the grammar penalty and the choice. no_speech_prob stays that of the raw, undivided row.
+ *   - tokens / n_tokens: the row's own sequence of this attempt (id, tid, p, plog, pt, ptsum; the rest as the getters
+ *     report them mid-attempt), without the prompt; n_tokens == 0 on the prefill row; a beam gets its own re-parented
+ *     history, a best_of candidate its own.
+ * The order of the rules is the one of oracle/oracle_whisper.cpp's restatement of whisper_process_logits; the upstream
+ * source could not be consulted offline. A call with a callback pays a host round trip of the rows per step and never
+ * decodes pipelined; its decoder launches are chosen as without one. NULL (the default): nothing new is allocated or
+ * launched. A batch above 128 clips runs as two halves on two threads: the second half's callbacks then come from its
+ * thread, serialised with the first half's.
+ *
+ * whisper_full_params.tdrz_enable is implemented: with it <|solm|> is not suppressed, and a segment whose
+ * token range holds one reports whisper_full_get_segment_speaker_turn_next* (and
+ * whisper_mi355x_batch_segment_speaker_turn_next) = true; the token's text appears only with print_special. false (the
+ * default): <|solm|> is suppressed and every segment reports false. No real tinydiarize model could be run offline: the
+ * field is tested with a callback that raises the token's logit.
+ *
+ * No field of whisper_full_params is ignored any more, but beam_search.patience, which upstream ignores as well.
  */
 #ifndef WHISPER_H
 #define WHISPER_H

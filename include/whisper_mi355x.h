@@ -96,6 +96,8 @@ WHISPER_API int64_t whisper_mi355x_batch_segment_t0(struct whisper_state * state
 WHISPER_API int64_t whisper_mi355x_batch_segment_t1(struct whisper_state * state, int job, int i_segment);
 WHISPER_API int whisper_mi355x_batch_segment_n_tokens(struct whisper_state * state, int job, int i_segment);
 WHISPER_API whisper_token_data whisper_mi355x_batch_token_data(struct whisper_state * state, int job, int i_segment, int i_token);
+/* whisper_full_get_segment_speaker_turn_next for a clip of the batch (whisper_full_params.tdrz_enable; false when off) */
+WHISPER_API bool whisper_mi355x_batch_segment_speaker_turn_next(struct whisper_state * state, int job, int i_segment);
 WHISPER_API int whisper_mi355x_batch_lang_id(struct whisper_state * state, int job);
 /* tokens generated (all decode steps, all attempts) by the last whisper_mi355x_full_batch */
 WHISPER_API long whisper_mi355x_batch_decoded_tokens(struct whisper_state * state);
@@ -251,6 +253,10 @@ WHISPER_API long whisper_mi355x_pdec_give_ups(struct whisper_state * state);
 #define WHISPER_MI355X_KSTAT_VAD_FRONTEND 102
 #define WHISPER_MI355X_KSTAT_VAD_LSTM 103
 #define WHISPER_MI355X_KSTAT_VAD_GATHER 104
+/* The stage kernel of whisper_full_params.logits_filter_callback (kernel-timing class 18, work in bytes: 8 per logit),
+ * out as for a class: one launch per logits launch of a call with a callback (but the top-k pass of a beam attempt's
+ * prefill, which reads the rows the prefill's greedy pass staged: one callback per row), none in a call without one. */
+#define WHISPER_MI355X_KSTAT_LOGITS_STAGE 105
 
 /* Kernel-level test/tuning hooks (device pointers): one fused-epilogue GEMM launch of the engine
  * (epi as in kernels.h: 0 store, 1 gelu, 2 residual f32, 4 f32, 5 cross K/V: out is then a cross cache of
@@ -490,6 +496,24 @@ WHISPER_API int whisper_mi355x_debug_logits_topk_gram(struct whisper_context * c
                                                       const int * rules, const float * temperature, int k, int split,
                                                       struct whisper_mi355x_cand * cand, struct whisper_mi355x_cand * greedy,
                                                       const uint32_t * deny, const uint32_t * gram, float penalty);
+
+/* Debug: the two halves of a logits launch of a call with whisper_full_params.logits_filter_callback (whisper.h), one
+ * launch each through the engine's launchers. flags bit 0: tdrz_enable (<|solm|> is not suppressed).
+ * logits_stage: logits = device [n][n_vocab] f32 (not written), out_rows = device [n][n_vocab] f32: row r after the
+ * rules that precede the callback, under ctl[r]. Nothing outside the n rows is written.
+ * logits_ex: whisper_mi355x_debug_logits (form as there) over raw = device [n][n_vocab]; filtered = device
+ * [n][n_vocab] makes it the prefiltered form (the rules that follow the callback over `filtered`, the no-speech
+ * probability from `raw`), NULL the plain form. logits_topk_ex: the same for whisper_mi355x_debug_logits_topk, with the
+ * rows' rules as ctl (want_probs is ignored). Return 0, -1 on bad arguments, or the runtime error code. */
+WHISPER_API int whisper_mi355x_debug_logits_stage(struct whisper_context * ctx, const float * logits, int n,
+                                                  const struct whisper_mi355x_seq_ctl * ctl, int flags, float * out_rows);
+WHISPER_API int whisper_mi355x_debug_logits_ex(struct whisper_context * ctx, const float * raw, const float * filtered, int n,
+                                               const struct whisper_mi355x_seq_ctl * ctl, int form, int flags,
+                                               struct whisper_mi355x_cand * out, float * probs);
+WHISPER_API int whisper_mi355x_debug_logits_topk_ex(struct whisper_context * ctx, const float * raw, const float * filtered,
+                                                    int n, const struct whisper_mi355x_seq_ctl * ctl, int k, int split,
+                                                    int flags, struct whisper_mi355x_cand * cand,
+                                                    struct whisper_mi355x_cand * greedy);
 
 /* ---- whisper_full_params.vad and the whisper_vad_* block (kernels/vad.hip) ----
  * With vad set, a call first filters its clips on the device: vad_frontend (one workgroup per clip and tile of four

@@ -421,8 +421,8 @@ int64_t whisper_full_get_segment_t0_from_state(struct whisper_state* s, int i) {
 int64_t whisper_full_get_segment_t0(struct whisper_context* ctx, int i) { return whisper_full_get_segment_t0_from_state(ctx->c.default_state, i); }
 int64_t whisper_full_get_segment_t1_from_state(struct whisper_state* s, int i) { auto g = seg(s, 0, i); return g ? g->t1 : 0; }
 int64_t whisper_full_get_segment_t1(struct whisper_context* ctx, int i) { return whisper_full_get_segment_t1_from_state(ctx->c.default_state, i); }
-bool whisper_full_get_segment_speaker_turn_next_from_state(struct whisper_state*, int) { return false; }
-bool whisper_full_get_segment_speaker_turn_next(struct whisper_context*, int) { return false; }
+bool whisper_full_get_segment_speaker_turn_next_from_state(struct whisper_state* s, int i) { auto g = seg(s, 0, i); return g && g->speaker_turn_next; }
+bool whisper_full_get_segment_speaker_turn_next(struct whisper_context* ctx, int i) { return whisper_full_get_segment_speaker_turn_next_from_state(ctx->c.default_state, i); }
 const char* whisper_full_get_segment_text_from_state(struct whisper_state* s, int i) { auto g = seg(s, 0, i); return g ? g->text.c_str() : nullptr; }
 const char* whisper_full_get_segment_text(struct whisper_context* ctx, int i) { return whisper_full_get_segment_text_from_state(ctx->c.default_state, i); }
 int whisper_full_n_tokens_from_state(struct whisper_state* s, int i) { auto g = seg(s, 0, i); return g ? (int)g->tokens.size() : 0; }
@@ -444,10 +444,7 @@ static whisper_token_data tdata(const Segment* g, int t) {
     whisper_token_data r;
     memset(&r, 0, sizeof(r));
     if (!g || t < 0 || t >= (int)g->tokens.size()) { r.id = -1; return r; }
-    const TokenData& x = g->tokens[t];
-    r.id = x.id; r.tid = x.tid; r.p = x.p; r.plog = x.plog; r.pt = x.pt; r.ptsum = x.ptsum;
-    r.t0 = x.t0; r.t1 = x.t1; r.t_dtw = x.t_dtw; r.vlen = x.vlen;  // (-1, -1, 0 without token_timestamps)
-    return r;
+    return token_data(g->tokens[t]);
 }
 whisper_token_data whisper_full_get_token_data_from_state(struct whisper_state* s, int i, int t) { return tdata(seg(s, 0, i), t); }
 whisper_token_data whisper_full_get_token_data(struct whisper_context* ctx, int i, int t) { return tdata(seg(ctx->c.default_state, 0, i), t); }
@@ -556,6 +553,7 @@ int64_t whisper_mi355x_batch_segment_t0(struct whisper_state* s, int job, int i)
 int64_t whisper_mi355x_batch_segment_t1(struct whisper_state* s, int job, int i) { auto g = seg(s, job, i); return g ? g->t1 : 0; }
 int whisper_mi355x_batch_segment_n_tokens(struct whisper_state* s, int job, int i) { auto g = seg(s, job, i); return g ? (int)g->tokens.size() : 0; }
 whisper_token_data whisper_mi355x_batch_token_data(struct whisper_state* s, int job, int i, int t) { return tdata(seg(s, job, i), t); }
+bool whisper_mi355x_batch_segment_speaker_turn_next(struct whisper_state* s, int job, int i) { auto g = seg(s, job, i); return g && g->speaker_turn_next; }
 int whisper_mi355x_batch_lang_id(struct whisper_state* s, int job) {
     return s && job >= 0 && job < (int)s->lang_ids.size() ? s->lang_ids[job] : -1;
 }
@@ -665,6 +663,7 @@ int whisper_mi355x_kernel_stats(struct whisper_state* s, int cls, double out[3])
         out[0] = k.ms; out[1] = (double)k.count; out[2] = k.work;
         return 0;
     }
+    if (cls == WHISPER_MI355X_KSTAT_LOGITS_STAGE) cls = K_LOGITS_STAGE;
     if (!s || cls < 0 || cls >= K_NCLASS) return -1;
     out[0] = s->kstat[cls].ms;
     out[1] = (double)s->kstat[cls].count;
@@ -1228,6 +1227,83 @@ int whisper_mi355x_debug_logits_gram(struct whisper_context* ctx, const float* l
         WM_CHECK(hipMemcpyAsync(out, d_out, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         if (d_probs) WM_CHECK(hipMemcpyAsync(probs, d_probs, pbytes, hipMemcpyDeviceToHost, st));
         WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+// ---- the halves of a logits launch around a logits_filter_callback --------------------------------
+static VocabIds hook_vid(struct whisper_context* ctx, int flags) {
+    VocabIds v = ctx->c.vid;
+    if (flags & 1) v.solm = -1;  // tdrz_enable: matches no id
+    return v;
+}
+int whisper_mi355x_debug_logits_stage(struct whisper_context* ctx, const float* logits, int n,
+                                      const struct whisper_mi355x_seq_ctl* ctl, int flags, float* out_rows) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !logits || !ctl || !out_rows || n <= 0) return -1;
+        hipSetDevice(ctx->c.device);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        SeqCtl* d_ctl = (SeqCtl*)b.get(n * sizeof(SeqCtl));
+        WM_CHECK(hipMemcpyAsync(d_ctl, ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
+        launch_logits_stage(logits, ctx->c.hp.n_vocab, d_ctl, n, hook_vid(ctx, flags), out_rows, st);
+        WM_CHECK(hipGetLastError());
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+int whisper_mi355x_debug_logits_ex(struct whisper_context* ctx, const float* raw, const float* filtered, int n,
+                                   const struct whisper_mi355x_seq_ctl* ctl, int form, int flags,
+                                   struct whisper_mi355x_cand* out, float* probs) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !raw || !ctl || !out || n <= 0 || form < 0 || form > 1) return -1;
+        for (int r = 0; r < n; r++)
+            if (ctl[r].want_probs && !probs) return -1;
+        hipSetDevice(ctx->c.device);
+        const int V = ctx->c.hp.n_vocab;
+        const size_t pbytes = (size_t)n * 2 * V * sizeof(float);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        SeqCtl* d_ctl = (SeqCtl*)b.get(n * sizeof(SeqCtl));
+        TokOut* d_out = (TokOut*)b.get(n * sizeof(TokOut));
+        float* d_probs = probs ? (float*)b.get(pbytes) : nullptr;
+        void* rec = form ? b.get(logits_rec_bytes(n)) : nullptr;
+        WM_CHECK(hipMemcpyAsync(d_ctl, ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
+        if (d_probs) WM_CHECK(hipMemsetAsync(d_probs, 0xff, pbytes, st));  // rows the kernel leaves alone read as NaN
+        launch_logits(raw, V, d_ctl, n, hook_vid(ctx, flags), d_out, d_probs, rec, nullptr, nullptr, 0.0f, st, filtered);
+        WM_CHECK(hipGetLastError());
+        WM_CHECK(hipMemcpyAsync(out, d_out, n * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        if (d_probs) WM_CHECK(hipMemcpyAsync(probs, d_probs, pbytes, hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+int whisper_mi355x_debug_logits_topk_ex(struct whisper_context* ctx, const float* raw, const float* filtered, int n,
+                                        const struct whisper_mi355x_seq_ctl* ctl, int k, int split, int flags,
+                                        struct whisper_mi355x_cand* cand, struct whisper_mi355x_cand* greedy) {
+    return guarded(nullptr, [&]() -> int {
+        if (!ctx || !raw || !ctl || !cand || !greedy || n <= 0 || k < 1 || k > kTopkMax) return -1;
+        hipSetDevice(ctx->c.device);
+        const int V = ctx->c.hp.n_vocab;
+        const VocabIds vid = hook_vid(ctx, flags);
+        HookBufs b;
+        HookStream hs;
+        hipStream_t st = hs.st;
+        SeqCtl* d_ctl = (SeqCtl*)b.get(n * sizeof(SeqCtl));
+        TokOut* d_out = (TokOut*)b.get((size_t)n * (kTopkMax + 1) * sizeof(TokOut));
+        void* rec = split ? b.get(logits_rec_bytes(n)) : nullptr;
+        WM_CHECK(hipMemcpyAsync(d_ctl, ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, st));
+        launch_logits(raw, V, d_ctl, n, vid, d_out + (size_t)n * kTopkMax, nullptr, rec, nullptr, nullptr, 0.0f, st, filtered);
+        launch_logits_topk(raw, V, d_ctl, n, vid, d_out, k, rec, nullptr, nullptr, 0.0f, st, filtered);
+        WM_CHECK(hipGetLastError());
+        std::vector<TokOut> out((size_t)n * (kTopkMax + 1));
+        WM_CHECK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(TokOut), hipMemcpyDeviceToHost, st));
+        WM_CHECK(hipStreamSynchronize(st));
+        for (int r = 0; r < n; r++) {
+            memcpy(&greedy[r], &out[(size_t)n * kTopkMax + r], sizeof(TokOut));
+            for (int q = 0; q < k; q++) memcpy(&cand[(size_t)r * k + q], &out[(size_t)r * kTopkMax + q], sizeof(TokOut));
+        }
         return 0;
     });
 }

@@ -203,6 +203,7 @@ static void reset_for_reuse(whisper_state* s) {
     s->mode = StepMode{};
     s->deny_on = false;
     s->gram_on = false;
+    s->filter_on = s->tdrz_on = false;
     s->ws.gd.host_masks.clear();
     s->ws.gd.rows_device = s->ws.gd.rows_patched = s->ws.gd.rows_host = 0;
     s->beam_info.clear();
@@ -334,6 +335,8 @@ static void free_ws(Workspace& w) {
     dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.kvstage); dfree(w.sctr);
     dfree(w.energy); dfree(w.tt_clips); dfree(w.tt_segs); dfree(w.tt_spans); dfree(w.deny); dfree(w.gram);
     if (w.h_gram) hipHostFree(w.h_gram);
+    dfree(w.frows);
+    if (w.h_frows) hipHostFree(w.h_frows);
     gram_dev_free(w.gd);
     vad_scratch_free(w.vad);
     if (w.h_sslot) hipHostFree(w.h_sslot);
@@ -444,8 +447,9 @@ static void ensure_ws_impl(Context* c, whisper_state* s, int n_jobs, int n_clips
         for (auto& a : s->align_info) a = {};  // (pointers into al_cost)
         if (w.h_ring) { WM_CHECK(hipHostFree(w.h_ring)); w.h_ring = nullptr; w.ring = nullptr; }
         dfree(w.sslot); dfree(w.cand); dfree(w.kvcp); dfree(w.sctr); dfree(w.gram);
+        dfree(w.frows);  // (sized by cap_jobs: ensure_filter_rows allocates them again for a call that has a callback)
         for (void** h : {(void**)&w.h_qtiles, (void**)&w.h_ints, (void**)&w.h_tout, (void**)&w.h_ctl, (void**)&w.h_sslot,
-                         (void**)&w.h_cand, (void**)&w.h_kvcp, (void**)&w.h_sctr, (void**)&w.h_gram})
+                         (void**)&w.h_cand, (void**)&w.h_kvcp, (void**)&w.h_sctr, (void**)&w.h_gram, (void**)&w.h_frows})
             if (*h) { void* q = *h; *h = nullptr; WM_CHECK(hipHostFree(q)); }
         w.cap_jobs = w.cap_tok = w.cap_cross = w.cap_xq = 0;
         // split-K slabs: decode steps (<= 128 rows per group, two concurrent groups) and the prefill
@@ -1604,6 +1608,16 @@ struct Sched {
     // grammar state of its sequence (fill_ctl -> ctl_upload)
     Grammar gram0;
     std::vector<const Grammar*> gram_rows;
+    // a call with a logits_filter_callback: per staged row of the coming logits launch its sequence, whose
+    // tokens are the history the callback gets (fill_ctl -> filter_round_trip), and the scratch they are converted into;
+    // filter_reuse: the coming launch reads the rows the last round trip left on the device (the prefill's top-k pass
+    // over rows whose callbacks have just run)
+    std::vector<const Seq*> filter_rows;
+    std::vector<whisper_token_data> filter_tokens;
+    bool filter_reuse = false;
+    // filter_fetched: the staged rows' copy to the host is already behind a synchronise (run_step enqueues it with the
+    // step's graph, so a step pays one synchronise before its callbacks, not two)
+    bool filter_fetched = false;
 };
 
 static double now_ms() {
@@ -1685,6 +1699,17 @@ static void fill_ctl(Sched& S, const Job& j, const Seq& q, int r, bool want_nosp
         if ((int)S.gram_rows.size() <= r) S.gram_rows.resize(r + 1, nullptr);
         S.gram_rows[r] = q.tokens.empty() ? &S.gram0 : &q.gram;
     }
+    if (S.s->filter_on) {
+        if ((int)S.filter_rows.size() <= r) S.filter_rows.resize(r + 1, nullptr);
+        S.filter_rows[r] = &q;
+    }
+}
+
+// whisper_full_params.tdrz_enable: a segment whose token range holds <|solm|> is followed by a speaker turn
+static void mark_speaker_turn(const Sched& S, Segment& g) {
+    if (!S.p.tdrz_enable) return;
+    for (const TokenData& t : g.tokens)
+        if (t.id == S.c->vocab.token_solm) g.speaker_turn_next = true;
 }
 
 static void finish_window(Sched& S, Job& j) {
@@ -1711,6 +1736,7 @@ static void finish_window(Sched& S, Job& j) {
                 if (!text.empty()) {
                     j.result.push_back({t0, t1, text, j.no_speech_prob, {}});
                     for (int k = i0; k <= i; k++) j.result.back().tokens.push_back(toks[k]);
+                    mark_speaker_turn(S, j.result.back());
                 }
                 text = "";
                 while (i < (int)toks.size() && toks[i].id > v.token_beg) i++;
@@ -1723,6 +1749,7 @@ static void finish_window(Sched& S, Job& j) {
             const int64_t t1 = j.seek + seek_delta;
             j.result.push_back({t0, t1, text, j.no_speech_prob, {}});
             for (int k = i0; k < (int)toks.size(); k++) j.result.back().tokens.push_back(toks[k]);
+            mark_speaker_turn(S, j.result.back());
         }
     }
     j.n_new_segments = (int)(j.result.size() - n_before);
@@ -2191,23 +2218,84 @@ static bool ctl_upload(Sched& S, int n) {
     WM_CHECK(hipMemcpyAsync(w.ctl, w.h_ctl, n * sizeof(SeqCtl), hipMemcpyHostToDevice, S.s->stream));
     return any_probs;
 }
-static void logits_launch(Context* c, whisper_state* s, int n) {
+// the launches' VocabIds: tdrz_enable keeps <|solm|> (its id matches no token, so no kernel code changes for it)
+static VocabIds call_vid(const Context* c, const whisper_state* s) {
+    VocabIds v = c->vid;
+    if (s->tdrz_on) v.solm = -1;
+    return v;
+}
+// The rules over the n rows' logits and the choice: the launch from before the callback existed (filtered null), or the
+// prefiltered form over the rows the callbacks left in ws.frows
+static void logits_rules(Context* c, whisper_state* s, int n, const float* filtered) {
     Workspace& w = s->ws;
     const uint32_t* deny = s->deny_on ? w.deny : nullptr;  // suppress_nst / suppress_regex (deny_prepare)
     const uint32_t* gram = s->gram_on ? w.gram : nullptr;  // the rows' grammar words (gram_upload)
     const float pen = s->gram_penalty;
+    const VocabIds vid = call_vid(c, s);
     if (s->mode.topk > 0) {  // a beam step: top-k candidates per row (candidate 0 = the greedy record of the row)
         KT kt(s, K_TOPK, (double)n * c->hp.n_vocab * 4);
-        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.cand, s->mode.topk, w.lrec, deny, gram, pen, s->stream);
+        launch_logits_topk(w.logits, c->hp.n_vocab, w.ctl, n, vid, w.cand, s->mode.topk, w.lrec, deny, gram, pen, s->stream, filtered);
         return;
     }
     KT kt(s, K_LOGITS, (double)n * c->hp.n_vocab * 4);
-    launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, c->vid, w.tout, w.probs, w.lrec, deny, gram, pen, s->stream);
+    launch_logits(w.logits, c->hp.n_vocab, w.ctl, n, vid, w.tout, w.probs, w.lrec, deny, gram, pen, s->stream, filtered);
+}
+// the tokens of a sampled step's rows drawn from their probs, the TokOut records rewritten in place
+static void sample_launch(Context* c, whisper_state* s, int n) {
+    Workspace& w = s->ws;
+    KT kt(s, K_SAMPLE, (double)n * c->hp.n_vocab * 4 * 2);
+    launch_sample(w.probs, c->hp.n_vocab, w.tout, w.tout, w.sctr, nullptr, s->sample_seed, c->vid.beg, n, s->stream);
+}
+// The logits launch of n staged rows. A call with a logits_filter_callback gets its first half only: the stage kernel
+// writes the rows after the pre-callback rules to ws.frows, and logits_finish goes on from there.
+static void logits_launch(Context* c, whisper_state* s, int n) {
+    if (!s->filter_on) {
+        logits_rules(c, s, n, nullptr);
+        return;
+    }
+    Workspace& w = s->ws;
+    KT kt(s, K_LOGITS_STAGE, (double)n * c->hp.n_vocab * 8);
+    launch_logits_stage(w.logits, c->hp.n_vocab, w.ctl, n, call_vid(c, s), w.frows, s->stream);
+}
+// the n staged rows' copy to the pinned host rows, in stream order behind the stage kernel
+static void filter_fetch(Sched& S, int n) {
+    Workspace& w = S.s->ws;
+    WM_CHECK(hipMemcpyAsync(w.h_frows, w.frows, (size_t)n * S.c->hp.n_vocab * sizeof(float), hipMemcpyDeviceToHost, S.s->stream));
+}
+// The staged rows to the host (the stream is drained by then), the caller's callback once per row in staged order, with
+// the row's own sequence of this attempt as its history, and the rows back to the device
+static void filter_round_trip(Sched& S, int n) {
+    Context* c = S.c;
+    whisper_state* s = S.s;
+    Workspace& w = s->ws;
+    const size_t V = c->hp.n_vocab;
+    if ((int)S.filter_rows.size() < n) WM_FAIL("logits filter: %d rows, %zu staged", n, S.filter_rows.size());
+    if (!S.filter_fetched) {
+        filter_fetch(S, n);
+        WM_CHECK(hipStreamSynchronize(s->stream));
+    }
+    S.filter_fetched = false;
+    for (int r = 0; r < n; r++) {
+        const Seq* q = S.filter_rows[r];
+        if (!q) WM_FAIL("logits filter: row %d of %d was not staged", r, n);
+        S.filter_tokens.clear();
+        for (const TokenData& t : q->tokens) S.filter_tokens.push_back(token_data(t));
+        S.p.logits_filter_callback(c->owner, s, S.filter_tokens.data(), (int)S.filter_tokens.size(), w.h_frows + (size_t)r * V,
+                                   S.p.logits_filter_callback_user_data);
+    }
+    WM_CHECK(hipMemcpyAsync(w.frows, w.h_frows, (size_t)n * V * sizeof(float), hipMemcpyHostToDevice, s->stream));
+}
+// The second half of a logits launch of a call with a callback: the round trip, the prefiltered form, a sampled step's draw
+static void logits_second_half(Sched& S, int n) {
+    if (!S.filter_reuse) filter_round_trip(S, n);
+    logits_rules(S.c, S.s, n, S.s->ws.frows);
+    if (S.s->mode.sample) sample_launch(S.c, S.s, n);
 }
 static void logits_finish(Sched& S, int n, bool any_probs, std::vector<std::vector<float>>& probs_rows) {
     Context* c = S.c;
     Workspace& w = S.s->ws;
     hipStream_t st = S.s->stream;
+    if (S.s->filter_on) logits_second_half(S, n);
     if (S.s->mode.topk > 0) {
         WM_CHECK(hipMemcpyAsync(w.h_cand, w.cand, (size_t)n * kTopkMax * sizeof(TokOut), hipMemcpyDeviceToHost, st));
         probs_rows.assign(n, {});
@@ -2275,7 +2363,8 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     for (auto& g : s->dec_graphs)
         if (g.n_tok == n && g.n_rows == n && g.mask == s->ktime_mask && g.direct == s->direct && g.sig == sig && g.pdec == pd &&
             g.par == par && g.beam == beam && g.actx == enc_ctx(c, s) && g.deny == s->deny_on && g.gram == s->gram_on &&
-            (!s->gram_on || g.gram_pen == s->gram_penalty) && (!s->mode.sample || g.seed == s->sample_seed))
+            (!s->gram_on || g.gram_pen == s->gram_penalty) && (!s->mode.sample || g.seed == s->sample_seed) &&
+            g.filt == s->filter_on && g.tdrz == s->tdrz_on)
             return &g;
     whisper_state::DecGraph g{n, n, s->ktime_mask, s->direct, sig, pd, gen, par, beam, nullptr, {}};
     g.seed = s->sample_seed;  // (a kernel argument of the draw below)
@@ -2283,16 +2372,14 @@ static whisper_state::DecGraph* dec_graph(Context* c, whisper_state* s, StepPlan
     g.deny = s->deny_on;
     g.gram = s->gram_on;
     g.gram_pen = s->gram_penalty;
+    g.filt = s->filter_on;
+    g.tdrz = s->tdrz_on;
     hipGraph_t graph;
     s->capture_ev = &g.ev;
     WM_CHECK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
     decoder_launch(c, s, P);
     logits_launch(c, s, n);
-    if (s->mode.sample) {  // the rows' tokens drawn from their probs, the TokOut records rewritten in place
-        Workspace& w = s->ws;
-        KT kt(s, K_SAMPLE, (double)n * c->hp.n_vocab * 4 * 2);
-        launch_sample(w.probs, c->hp.n_vocab, w.tout, w.tout, w.sctr, nullptr, s->sample_seed, c->vid.beg, n, s->stream);
-    }
+    if (s->mode.sample && !s->filter_on) sample_launch(c, s, n);  // (with a callback: after it, logits_second_half)
     if (par > 0) {
         Workspace& w = s->ws;
         char* slot = w.ring + (par - 1) * ring_slot_bytes(w);
@@ -2375,15 +2462,24 @@ static void run_step(Sched& S, int n, bool any_probs, std::vector<std::vector<fl
     // A persistent launch needs its 256 workgroups resident together: persistent steps of different states
     // (threads) of this process on one device never overlap, so two of them cannot hold half the CUs each
     // (steps on different devices do not wait for each other)
+    // (a call with a logits_filter_callback: the lock goes when the graph has run, before the callbacks; a launch that
+    // gave up has staged nothing usable, so its re-run comes first and is the one whose rows the callbacks see)
     bool gave_up;
     {
         PdecRunLock lk(c->device, G->pdec != 0);
         WM_CHECK(hipGraphLaunch(G->exec, s->stream));
-        logits_finish(S, n, any_probs, probs_rows);
+        if (s->filter_on) {
+            filter_fetch(S, n);
+            WM_CHECK(hipStreamSynchronize(s->stream));
+        } else logits_finish(S, n, any_probs, probs_rows);
         gave_up = G->pdec && *s->ws.h_pd_err != 0;
     }
     kt_flush_graph(s, *G);
-    if (gave_up) rerun_given_up(S, n, any_probs, probs_rows, t_step);
+    if (gave_up) rerun_given_up(S, n, any_probs, probs_rows, t_step);  // (stages and fetches its own rows)
+    else if (s->filter_on) {
+        S.filter_fetched = true;
+        logits_finish(S, n, any_probs, probs_rows);
+    }
 }
 
 // Pipelined greedy decoding. The per-step path waits for a step's 32-byte results before it launches the next
@@ -2410,6 +2506,7 @@ static bool pipe_on() {  // (read per call: tests compare both paths in one proc
 static bool pipe_ok(Sched& S, const std::vector<int>& act) {
     if (!pipe_on() || S.o.forced || (S.o.spot_logits && S.o.n_spot > 0)) return false;
     if (S.s->gram_on) return false;  // the host advances the grammar after every step
+    if (S.s->filter_on) return false;  // the host's callback sits in the middle of every step's logits rules
     for (size_t k = 0; k < S.jobs.size(); k++) {
         const Job& j = S.jobs[k];
         if (j.phase == PH_DONE) continue;
@@ -3120,9 +3217,15 @@ static int pass_prefill(Sched& S) {
         for (int k : act) any_beam |= beam_attempt(S, S.jobs[k]);
         if (any_beam) {  // the same rows again through the top-k form (candidate 0 = the record above)
             ModeScope mode(s, StepMode{S.beam_k, false, false});
-            logits_launch(c, s, na);
             std::vector<std::vector<float>> none;
-            logits_finish(S, na, false, none);
+            if (s->filter_on) {  // the rows the callbacks just edited are on the device: no second call per row
+                S.filter_reuse = true;
+                try { logits_finish(S, na, false, none); } catch (...) { S.filter_reuse = false; throw; }
+                S.filter_reuse = false;
+            } else {
+                logits_launch(c, s, na);
+                logits_finish(S, na, false, none);
+            }
         }
     }
     copy_spot_logits(S, act);
@@ -3281,6 +3384,15 @@ int deny_lookup(Context* c, bool suppress_nst, const char* regex, std::vector<ui
     }
     if (words) *words = c->deny_words;
     return 0;
+}
+
+// The rows of a call with a logits_filter_callback, for the workspace's cap_jobs rows (after ensure_ws; kept with the
+// workspace: a call without a callback allocates nothing)
+static void ensure_filter_rows(Context* c, whisper_state* s) {
+    Workspace& w = s->ws;
+    const size_t bytes = (size_t)w.cap_jobs * c->hp.n_vocab * sizeof(float);
+    if (!w.frows) dalloc(w.frows, bytes);
+    if (!w.h_frows) WM_CHECK(hipHostMalloc((void**)&w.h_frows, bytes, 0));
 }
 
 // The call's mask into the state's buffer, on its stream, before the first logits launch: nothing when the call has
@@ -3474,6 +3586,8 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
     s->gram_on = s->gram_rules.on();
     s->gram_penalty = p.grammar_penalty;
     S.gram0.init(s->gram_rules);
+    s->filter_on = p.logits_filter_callback != nullptr;
+    s->tdrz_on = p.tdrz_enable;
     ensure_expanded(c, s->stream);  // quantized files: before anything is captured
     S.hyps.resize(S.beam_k > 0 || S.sample_n > 1 ? n_jobs : 0);
     s->beam_info.assign(n_jobs, {});
@@ -3503,6 +3617,7 @@ static int full_batch_one(Context* c, whisper_state* s, const whisper_full_param
         ensure_ws(c, s, n_jobs * std::max(1, std::max(S.beam_k, S.sample_n)), n_jobs);
         if (!single_api) s->audio_ctx = 0;  // every clip of the batch API starts as on a fresh state (apply_audio_ctx)
         if (const int r = deny_prepare(c, s, p)) return r;
+        if (s->filter_on) ensure_filter_rows(c, s);
         if (s->gram_on) gram_dev_rules(s->ws.gd, s->gram_rules, s->stream);
         compute_mel(c, s, pcm, n, n_jobs, on_device);
     }
@@ -3682,6 +3797,19 @@ int full_batch(Context* c, whisper_state* s, const whisper_full_params& p, const
             return g->cb(g->ud);
         };
         pp.abort_callback_user_data = &gate;
+    }
+    // ... nor the logits filter callback; both halves report the caller's state (the second half calls it from its own
+    // thread: INTEGRATION.md)
+    struct FilterGate { std::mutex mu; whisper_logits_filter_callback cb; void* ud; whisper_state* st; }
+        fgate{{}, p.logits_filter_callback, p.logits_filter_callback_user_data, s};
+    if (p.logits_filter_callback) {
+        pp.logits_filter_callback = [](whisper_context* cx, whisper_state*, const whisper_token_data* tokens, int n_tokens,
+                                       float* logits, void* u) {
+            FilterGate* g = (FilterGate*)u;
+            std::lock_guard<std::mutex> lk(g->mu);
+            g->cb(cx, g->st, tokens, n_tokens, logits, g->ud);
+        };
+        pp.logits_filter_callback_user_data = &fgate;
     }
     // teacher forcing (a parity-test hook) by halves: each half sees its own jobs' forced rows, and the spot
     // jobs of the other half never match (-1); both write their own rows of the caller's spot_logits

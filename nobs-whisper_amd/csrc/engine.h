@@ -4,6 +4,7 @@
 #include <map>
 #include <memory>
 #include <atomic>
+#include <cstring>
 #include <mutex>
 #include <random>
 #include <string>
@@ -201,12 +202,22 @@ struct TokenData {
     int64_t t0 = -1, t1 = -1;
     float vlen = 0.0f;
 };
+// a token as whisper.h reports it (the getters; the history a logits_filter_callback gets)
+inline whisper_token_data token_data(const TokenData& x) {
+    whisper_token_data r;
+    memset(&r, 0, sizeof(r));
+    r.id = x.id; r.tid = x.tid; r.p = x.p; r.plog = x.plog; r.pt = x.pt; r.ptsum = x.ptsum;
+    r.t0 = x.t0; r.t1 = x.t1; r.t_dtw = x.t_dtw; r.vlen = x.vlen;  // (-1, -1, 0 without token_timestamps)
+    return r;
+}
 
 struct Segment {
     int64_t t0, t1;
     std::string text;
     float no_speech_prob;
     std::vector<TokenData> tokens;
+    // whisper_full_params.tdrz_enable: a <|solm|> token lies in the segment's token range (false when the field is off)
+    bool speaker_turn_next = false;
 };
 
 // Workspace sized for a batch of up to `cap_jobs` clips; grows on demand, never shrinks.
@@ -250,6 +261,10 @@ struct Workspace {
     uint32_t* gram = nullptr;
     uint32_t* h_gram = nullptr;
     GramDev gd;
+    // whisper_full_params.logits_filter_callback (allocated by the first call that has one, for cap_jobs
+    // rows, so a captured step's pointer lives as long as its graph): the rows after the pre-callback rules
+    // [cap_jobs][n_vocab] f32, and the pinned rows the callback edits
+    float *frows = nullptr, *h_frows = nullptr;
     int *win_job = nullptr, *win_seek = nullptr, *win_slot = nullptr;
     // persistent decode step: the hand-off block (granules + error word) and the error word's host copy
     unsigned* pd_sync = nullptr;
@@ -308,7 +323,7 @@ struct Workspace {
 // Live per-kernel-class timing with HIP events on the state's stream (bench.py's roofline leg).
 // `work` is the algorithmic FLOPs (MFMA-bound classes) or HBM bytes (HBM-bound classes).
 enum KClass { K_GEMM_ENC = 0, K_ATTN_ENC, K_ATTN_CROSS, K_ATTN_SELF, K_GEMM_DEC, K_LOGITS, K_MEL, K_PDEC, K_OTHER,
-              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_GRAMMAR, K_VAD, K_NCLASS };
+              K_ALIGN_SCORES, K_ALIGN_COST, K_ALIGN_DTW, K_TOPK, K_KV_GATHER, K_SAMPLE, K_TOKTS, K_GRAMMAR, K_VAD, K_LOGITS_STAGE, K_NCLASS };
 struct KStat { double ms = 0, work = 0; long count = 0; };
 
 // What a decode step does besides greedy's plain step (whisper_state::mode; all off between steps). topk > 0: the
@@ -389,7 +404,9 @@ struct whisper_state {
     // argument)
     // (gram, gram_pen: the logits launch reads the grammar's reject words, whisper_state::gram_on, and the penalty is a
     // kernel argument)
-    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; bool deny = false; bool gram = false; float gram_pen = 0.0f; };
+    // (filt: the call has a logits_filter_callback, whisper_state::filter_on: the graph ends with the stage kernel, and the
+    // rest of the step follows the callbacks as plain launches; tdrz: tdrz_enable, the VocabIds argument keeps solm)
+    struct DecGraph { int n_tok, n_rows, mask; bool direct; int sig; int pdec; int gen; int par; int beam; hipGraphExec_t exec; std::vector<KPending> ev; uint64_t seed = 0; int actx = 0; bool deny = false; bool gram = false; float gram_pen = 0.0f; bool filt = false; bool tdrz = false; };
     std::vector<DecGraph> dec_graphs;
     std::vector<KPending>* capture_ev = nullptr;  // non-null while a decode step is being captured
     double cur_self_work = 0;                     // self-attention bytes of the current step
@@ -411,6 +428,9 @@ struct whisper_state {
     bool gram_on = false;
     wm::GrammarRules gram_rules;
     float gram_penalty = 0.0f;
+    // the current call has a logits_filter_callback: a logits launch is the stage kernel, and the
+    // prefiltered form follows the callbacks (engine.cpp logits_finish); tdrz_on: tdrz_enable, solm is not suppressed
+    bool filter_on = false, tdrz_on = false;
     // beam_info[job] = the beams of the job's last beam-searched window (whisper_mi355x_beam_info)
     struct BeamRec { std::vector<int> tokens; double sum_logprobs_all = 0; int flags = 0; };
     std::vector<std::vector<BeamRec>> beam_info;

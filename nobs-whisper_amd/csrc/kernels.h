@@ -325,7 +325,7 @@ struct TokOut { int id, tid; float p, plog, pt, ptsum, nosp_prob, pad; };
 // existed. With gram the launch takes the one-workgroup-per-row form whatever n_seq is (also launch_logits_topk).
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v,
                    TokOut* out, float* probs, void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty,
-                   hipStream_t st);
+                   hipStream_t st, const float* filtered = nullptr);
 size_t logits_rec_bytes(int n_seq);
 // Top-k after the rules (beam search): the k <= kTopkMax most probable tokens of every row, p > 0, in
 // (p descending, id ascending) order, as TokOut records cand[row * kTopkMax + j]; j = 0 repeats the record
@@ -333,7 +333,18 @@ size_t logits_rec_bytes(int n_seq);
 // a record j > 0 without a token has id = -1. Rows are t = 0 rows (want_probs is ignored).
 constexpr int kTopkMax = 8;
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
-                        void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st);
+                        void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st,
+                        const float* filtered = nullptr);
+// whisper_full_params.logits_filter_callback. The rules of a row come in two halves with the caller's
+// callback between them: launch_logits_stage writes out[row][n_vocab] (f32, row stride n_vocab) = the row after the
+// temperature divide, suppress_blank, <|notimestamps|>, no_timestamps, sot / nosp / solm / translate / transcribe / prev
+// and the language tokens (solm is kept when v.solm matches no id: tdrz_enable); logits is not written. `filtered` of
+// launch_logits / launch_logits_topk (null: the launch from before the callback existed) is such a buffer after the
+// callback: the launch is then the prefiltered form, which skips the divide and those rules, applies every other rule
+// to the filtered row and takes the no-speech probability from the raw row `logits`. Being prefiltered is a property of
+// the launch, not of a row: SeqCtl does not change.
+void launch_logits_stage(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, float* out,
+                         hipStream_t st);
 // ---- the grammar's reject masks (kernels/grammar.hip) -------------------------------------------------
 // What the kernel takes of a row's grammar state, and a token's working set (stacks per token, depth): a state or a
 // token's simulation beyond them is the host's (grammar_reject).

@@ -11,6 +11,11 @@
 // log-softmax again (gram_penalized; only when the call has a grammar); probs = exp(logprob). Greedy argmax keeps whisper's first-index tie break over
 // the float probs. When temperature > 0 the probs row is also written for host-side sampling
 // (std::discrete_distribution, exactly as whisper.cpp samples).
+// A call with whisper_full_params.logits_filter_callback runs the rules as two launches with the host's
+// callback between them, where upstream calls it: logits_stage_kernel applies the rules up to and including the language
+// tokens (pre_logit) and writes the rows for the host; the prefiltered form of the kernels below (PF) applies the rest,
+// from the deny mask on (post_logit), to the rows the callback left. With tdrz_enable the launches' VocabIds carry a solm
+// id that matches no token.
 // This file is compiled with -ffp-contract=off.
 #include "../common.h"
 #include "../kernels.h"
@@ -19,11 +24,13 @@ namespace wm {
 
 static constexpr int LT = 1024;
 
-__device__ __forceinline__ float masked_logit(float x, int i, const SeqCtl& c, const VocabIds& v) {
+// masked_logit in the two halves whisper_full_params.logits_filter_callback sits between: pre_logit is
+// what the callback's row has been through, post_logit what follows it. A masked entry is -inf and stays -inf, so
+// masked_logit(x) = post_logit(pre_logit(x)) in every bit.
+__device__ __forceinline__ float pre_logit(float x, int i, const SeqCtl& c, const VocabIds& v) {
     if (c.temperature > 0.0f) x = x / c.temperature;
-    // text tokens (every special id is >= eot): only the blank and the timestamp-pairing rules reach them
+    // text tokens (every special id is >= eot): only the blank rule reaches them
     if (i < v.eot) {
-        if (c.last_ts && !c.penult_ts) return -INFINITY;
         if (c.suppress_blank && c.is_initial && i == v.space) return -INFINITY;
         return x;
     }
@@ -32,6 +39,14 @@ __device__ __forceinline__ float masked_logit(float x, int i, const SeqCtl& c, c
     if (c.no_timestamps && i >= v.beg) return -INFINITY;
     if (i == v.sot || i == v.nosp || i == v.solm || i == v.translate || i == v.transcribe || i == v.prev) return -INFINITY;
     if (i > v.sot && i <= v.sot + v.n_lang) return -INFINITY;
+    return x;
+}
+__device__ __forceinline__ float post_logit(float x, int i, const SeqCtl& c, const VocabIds& v) {
+    // text tokens: only the timestamp-pairing rule reaches them
+    if (i < v.eot) {
+        if (c.last_ts && !c.penult_ts) return -INFINITY;
+        return x;
+    }
     if (c.suppress_eot && i == v.eot) return -INFINITY;
     if (c.last_ts) {
         if (c.penult_ts) { if (i >= v.beg) return -INFINITY; }
@@ -41,17 +56,27 @@ __device__ __forceinline__ float masked_logit(float x, int i, const SeqCtl& c, c
     if (c.has_ts && i >= v.beg && i < v.beg + c.seek_delta / 2) return -INFINITY;
     return x;
 }
+__device__ __forceinline__ float masked_logit(float x, int i, const SeqCtl& c, const VocabIds& v) {
+    return post_logit(pre_logit(x, i, c, v), i, c, v);
+}
+// PF: the launch is the prefiltered form: its rows went through pre_logit (the stage kernel) and the caller's
+// logits_filter_callback, so only post_logit is left. false: the launch is the one from before the callback existed.
+template <bool PF>
+__device__ __forceinline__ float rule_logit(float x, int i, const SeqCtl& c, const VocabIds& v) {
+    if constexpr (PF) return post_logit(x, i, c, v);
+    else return masked_logit(x, i, c, v);
+}
 
 // DM: the deny mask of suppress_nst / suppress_regex: bit i & 31 of word i >> 5 set = token i is
 // denied, whatever the other rules say. 0: no mask (deny is not read: the code of a launch without one is what it
 // was before the mask existed), 1: deny is the device buffer, read through the cache, 2: deny is the workgroup's
 // copy in LDS. i < n_vocab.
-template <int DM>
+template <int DM, bool PF = false>
 __device__ __forceinline__ float masked_deny(float x, int i, const SeqCtl& c, const VocabIds& v, const uint32_t* deny) {
     if constexpr (DM != 0) {
         if ((deny[i >> 5] >> (i & 31)) & 1u) return -INFINITY;
     }
-    return masked_logit(x, i, c, v);
+    return rule_logit<PF>(x, i, c, v);
 }
 
 // GM: the grammar's reject mask (whisper_full_params.grammar_rules): gram = the row's words, bit i & 31 of
@@ -176,28 +201,12 @@ static size_t row_lds_bytes(int dm, int n_vocab) {
 // tokens with p > 0 in (p descending, id ascending) order. A text candidate carries the row's tid / pt / ptsum, a
 // timestamp candidate tid = id and pt = p (as the greedy record does); when fewer than topk tokens have p > 0
 // the remaining records have id = -1.
-template <int DM, int GM, bool TOPK>
-__global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
-                                                    VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs, int topk,
-                                                    const uint32_t* __restrict__ deny, const uint32_t* __restrict__ gram,
-                                                    float penalty) {
-    const int s = blockIdx.x;
-    const SeqCtl c = ctl[s];
-    const float* L = logits + (long)s * ld;
-    constexpr int NW = LT / 64;
-    const int n = v.n_vocab, tid = threadIdx.x;
-    __shared__ float shf[NW];
-    __shared__ int shi[NW];
-    __shared__ double shd[NW];
-    __shared__ TokOut s_top[2];  // TOPK: the greedy record; [1].tid / .pt: the row's tid / pt (a text candidate's)
-
-    extern __shared__ float s_row[];  // [NPT_LDS][LT]
-    RowSlice x{s_row};
-    DenyLane<DM> dl;
-    dl.load(deny, s_row, n);
-    const uint32_t* dm = dl.words;
-    // the register part first, then the LDS part in batches of 12 loads in flight (a load -> LDS
-    // store pair per element would wait out one memory latency per element)
+// PF (the prefiltered form): filt [n_seq][n_vocab] holds the rows after pre_logit and the caller's callback; the raw row
+// is read only for the no-speech probability, the filtered one is then loaded over it.
+// Row `row` of the launch into a thread's slice: the register part first, then the LDS part in batches of 12 loads in
+// flight (a load -> LDS store pair per element would wait out one memory latency per element)
+__device__ __forceinline__ void load_row(RowSlice& x, const float* __restrict__ L, int n) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int k = NPT_LDS; k < NPT; k++) {
         const int i = tid + k * LT;
@@ -214,6 +223,33 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
 #pragma unroll
         for (int k = 0; k < 12; k++) x.set(k0 + k, t[k]);
     }
+}
+template <int DM, int GM, bool TOPK, bool PF>
+__global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ logits, long ld, const SeqCtl* __restrict__ ctl,
+                                                    VocabIds v, TokOut* __restrict__ out, float* __restrict__ probs, int topk,
+                                                    const uint32_t* __restrict__ deny, const uint32_t* __restrict__ gram,
+                                                    float penalty, const float* __restrict__ filt) {
+    const int s = blockIdx.x;
+    const SeqCtl c = ctl[s];
+    const float* R = logits + (long)s * ld;                   // the raw row (the no-speech probability)
+    const float* L = PF ? filt + (long)s * v.n_vocab : R;     // the row the rules read
+    constexpr int NW = LT / 64;
+    const int n = v.n_vocab, tid = threadIdx.x;
+    __shared__ float shf[NW];
+    __shared__ int shi[NW];
+    __shared__ double shd[NW];
+    __shared__ TokOut s_top[2];  // TOPK: the greedy record; [1].tid / .pt: the row's tid / pt (a text candidate's)
+
+    extern __shared__ float s_row[];  // [NPT_LDS][LT]
+    RowSlice x{s_row};
+    DenyLane<DM> dl;
+    dl.load(deny, s_row, n);
+    const uint32_t* dm = dl.words;
+    if constexpr (PF) {
+        if (c.want_nosp) load_row(x, R, n);
+    } else {
+        load_row(x, L, n);
+    }
     float nosp_prob = 0.0f;
     if (c.want_nosp) {  // no-speech probability from the raw (unfiltered) logits
         float mx = -INFINITY;
@@ -227,15 +263,16 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
             if (tid + k * LT < n) sm += __expf(x.get(k) - mx);
         sm = blk_sum<NW>(sm, shf);
         const float lse = logf(sm) + mx;
-        nosp_prob = expf(L[v.nosp] - lse);
+        nosp_prob = expf(R[v.nosp] - lse);
     }
+    if constexpr (PF) load_row(x, L, n);  // (a thread overwrites its own slice only)
     // filtered logits, in place
     dl.store(s_row, n);
     if constexpr (DM == 2) __syncthreads();  // the mask's LDS copy
 #pragma unroll
     for (int k = 0; k < NPT; k++) {
         const int i = tid + k * LT;
-        if (i < n) x.set(k, dl.denied(k) ? -INFINITY : masked_logit(x.get(k), i, c, v));
+        if (i < n) x.set(k, dl.denied(k) ? -INFINITY : rule_logit<PF>(x.get(k), i, c, v));
     }
     // log-softmax of the filtered logits
     float mx = -INFINITY;
@@ -325,7 +362,7 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
         r.id = best > 0.0f ? ibest : 0;
         r.p = best;
         {
-            float xv = masked_deny<DM>(L[r.id], r.id, c, v, dm);
+            float xv = masked_deny<DM, PF>(L[r.id], r.id, c, v, dm);
             if constexpr (GM != 0) { if (grow) xv = gram_penalized<GM>(xv, r.id, v, grow, penalty); }
             if (mask_text && r.id < v.beg) xv = -INFINITY;
             r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
@@ -369,11 +406,11 @@ __global__ void __launch_bounds__(LT) logits_kernel(const float* __restrict__ lo
                 } else {
                     r.id = ij;
                     r.p = bj;
-                    r.plog = masked_deny<DM>(L[ij], ij, c, v, dm) - lse;  // p > 0: the filtered logit is finite
+                    r.plog = masked_deny<DM, PF>(L[ij], ij, c, v, dm) - lse;  // p > 0: the filtered logit is finite
                     // (masked_deny a second time, on thread 0 once per round, not a temporary shared with the line
                     // above: through one the GM = 0 instantiations' register allocation changed)
                     if constexpr (GM != 0) {
-                        if (grow) r.plog = gram_penalized<GM>(masked_deny<DM>(L[ij], ij, c, v, dm), ij, v, grow, penalty) - lse;
+                        if (grow) r.plog = gram_penalized<GM>(masked_deny<DM, PF>(L[ij], ij, c, v, dm), ij, v, grow, penalty) - lse;
                     }
                     if (ij >= v.beg) { r.tid = ij; r.pt = bj; }
                     else { r.tid = s_top[1].tid; r.pt = s_top[1].pt; }
@@ -408,22 +445,26 @@ size_t logits_rec_bytes(int n_seq) { return (size_t)std::max(1, n_seq) * KS * si
 
 // (DM 0 / 1 in the split form's 256-thread kernels: a chunk workgroup needs ~102 words of the mask once each, so
 // they come through the cache)
-template <int DM>
+template <int DM, bool PF>
 __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restrict__ logits, long ld,
                                                           const SeqCtl* __restrict__ ctl, VocabIds v,
-                                                          LogitRec* __restrict__ rec, const uint32_t* __restrict__ dm) {
+                                                          LogitRec* __restrict__ rec, const uint32_t* __restrict__ dm,
+                                                          const float* __restrict__ filt) {
     constexpr int NW = LT2 / 64, PER = 14;  // 14 * 256 * 16 >= 51866
     const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
-    const float* L = logits + (long)s * ld;
+    const float* R = logits + (long)s * ld;
+    const float* L = PF ? filt + (long)s * n : R;
     const int cs = (n + KS - 1) / KS, i0 = c * cs, i1 = min(n, i0 + cs);
     __shared__ float shf[NW];
     __shared__ int shi[NW];
     float raw[PER];
+    if (!PF || q.want_nosp) {  // (PF: the raw row serves the no-speech sums only)
 #pragma unroll
-    for (int k = 0; k < PER; k++) {
-        const int i = i0 + tid + k * LT2;
-        raw[k] = i < i1 ? L[i] : -INFINITY;
+        for (int k = 0; k < PER; k++) {
+            const int i = i0 + tid + k * LT2;
+            raw[k] = i < i1 ? R[i] : -INFINITY;
+        }
     }
     uint32_t dw[DM ? PER : 1];  // the mask's words of this thread's ids, in flight with the row
     if constexpr (DM != 0) {
@@ -447,6 +488,13 @@ __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restric
         r.m_r = mx;
         r.s_r = blk_sum<NW>(sm, shf);
     }
+    if constexpr (PF) {
+#pragma unroll
+        for (int k = 0; k < PER; k++) {
+            const int i = i0 + tid + k * LT2;
+            raw[k] = i < i1 ? L[i] : -INFINITY;
+        }
+    }
     float m = -INFINITY, mts = -INFINITY, mtx = -INFINITY;
     int ix = 0x7fffffff, its = 0x7fffffff;
 #pragma unroll
@@ -454,7 +502,7 @@ __global__ void __launch_bounds__(LT2) logits_part_kernel(const float* __restric
         const int i = i0 + tid + k * LT2;
         bool denied = false;
         if constexpr (DM != 0) denied = (dw[k] >> (i & 31)) & 1u;
-        const float x = i < i1 && !denied ? masked_logit(raw[k], i, q, v) : -INFINITY;
+        const float x = i < i1 && !denied ? rule_logit<PF>(raw[k], i, q, v) : -INFINITY;
         raw[k] = x;
         if (x > -INFINITY) {
             argmax_pair(m, ix, x, i);
@@ -490,23 +538,24 @@ struct RowRec {
     int tid;   // the row's tid / pt (a text candidate's)
     float pt;
 };
-template <int DM>
-__device__ __forceinline__ RowRec combine_recs(const float* L, int s, const SeqCtl& q, const VocabIds& v, const LogitRec* rec,
-                                               const uint32_t* dm) {
-    const LogitRec* R = rec + (long)s * KS;
+// (L: the row the rules read, R: the raw row; one row unless the launch is the prefiltered form)
+template <int DM, bool PF>
+__device__ __forceinline__ RowRec combine_recs(const float* L, const float* R, int s, const SeqCtl& q, const VocabIds& v,
+                                               const LogitRec* rec, const uint32_t* dm) {
+    const LogitRec* C = rec + (long)s * KS;
     float M = -INFINITY, Mts = -INFINITY, Mtx = -INFINITY, Mr = -INFINITY;
     int ix = 0x7fffffff, its = 0x7fffffff;
     for (int c = 0; c < KS; c++) {
-        argmax_pair(M, ix, R[c].m, R[c].ix_all);
-        argmax_pair(Mts, its, R[c].m_ts, R[c].ix_ts);
-        Mtx = fmaxf(Mtx, R[c].m_text);
-        Mr = fmaxf(Mr, R[c].m_r);
+        argmax_pair(M, ix, C[c].m, C[c].ix_all);
+        argmax_pair(Mts, its, C[c].m_ts, C[c].ix_ts);
+        Mtx = fmaxf(Mtx, C[c].m_text);
+        Mr = fmaxf(Mr, C[c].m_r);
     }
     float S = 0.0f, Sts = 0.0f, Sr = 0.0f;
     for (int c = 0; c < KS; c++) {
-        if (R[c].m > -INFINITY) S += R[c].s * expf(R[c].m - M);
-        if (R[c].m_ts > -INFINITY) Sts += R[c].s_ts * expf(R[c].m_ts - Mts);
-        if (q.want_nosp && R[c].m_r > -INFINITY) Sr += R[c].s_r * expf(R[c].m_r - Mr);
+        if (C[c].m > -INFINITY) S += C[c].s * expf(C[c].m - M);
+        if (C[c].m_ts > -INFINITY) Sts += C[c].s_ts * expf(C[c].m_ts - Mts);
+        if (q.want_nosp && C[c].m_r > -INFINITY) Sr += C[c].s_r * expf(C[c].m_r - Mr);
     }
     RowRec o;
     const float lse = logf(S) + M;
@@ -520,7 +569,7 @@ __device__ __forceinline__ RowRec combine_recs(const float* L, int s, const SeqC
     r.id = best > 0.0f ? ib : 0;
     r.p = best;
     {
-        float xv = masked_deny<DM>(L[r.id], r.id, q, v, dm);
+        float xv = masked_deny<DM, PF>(L[r.id], r.id, q, v, dm);
         if (mask_text && r.id < v.beg) xv = -INFINITY;
         r.plog = xv > -INFINITY ? xv - lse : -INFINITY;
     }
@@ -532,7 +581,7 @@ __device__ __forceinline__ RowRec combine_recs(const float* L, int s, const SeqC
     o.tid = r.tid;
     o.pt = r.pt;
     if (r.id >= v.beg) { r.tid = r.id; r.pt = r.p; }
-    r.nosp_prob = q.want_nosp ? expf(L[v.nosp] - (logf(Sr) + Mr)) : 0.0f;
+    r.nosp_prob = q.want_nosp ? expf(R[v.nosp] - (logf(Sr) + Mr)) : 0.0f;
     r.pad = 0.0f;
     o.r = r;
     o.lse = lse;
@@ -541,18 +590,20 @@ __device__ __forceinline__ RowRec combine_recs(const float* L, int s, const SeqC
     return o;
 }
 
-template <int DM>
+template <int DM, bool PF>
 __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __restrict__ logits, long ld,
                                                              const SeqCtl* __restrict__ ctl, VocabIds v,
                                                              const LogitRec* __restrict__ rec, TokOut* __restrict__ out,
-                                                             float* __restrict__ probs, const uint32_t* __restrict__ dm) {
+                                                             float* __restrict__ probs, const uint32_t* __restrict__ dm,
+                                                             const float* __restrict__ filt) {
     const int s = blockIdx.x, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
-    const float* L = logits + (long)s * ld;
+    const float* R = logits + (long)s * ld;
+    const float* L = PF ? filt + (long)s * n : R;
     __shared__ float sh_lse;
     __shared__ int sh_mask;
     if (tid == 0) {
-        const RowRec c = combine_recs<DM>(L, s, q, v, rec, dm);
+        const RowRec c = combine_recs<DM, PF>(L, R, s, q, v, rec, dm);
         out[s] = c.r;
         sh_lse = c.lse;
         sh_mask = c.mask_text;
@@ -562,7 +613,7 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
     const float lse = sh_lse;
     const bool mask_text = sh_mask;
     for (int i = tid; i < n; i += LT2) {
-        float xv = masked_deny<DM>(L[i], i, q, v, dm);
+        float xv = masked_deny<DM, PF>(L[i], i, q, v, dm);
         if (mask_text && i < v.beg) xv = -INFINITY;
         probs[(long)s * 2 * n + i] = xv == -INFINITY ? 0.0f : __expf(xv - lse);
         probs[(long)s * 2 * n + n + i] = xv == -INFINITY ? -INFINITY : xv - lse;
@@ -576,14 +627,16 @@ __global__ void __launch_bounds__(LT2) logits_combine_kernel(const float* __rest
 // timestamp rule fired) without the earlier winners, with p = e^(x - lse), plog = x - lse: the split form's own
 // key (it orders by x where the one-workgroup form orders by the rounded p). A candidate whose p underflows
 // to 0, and every one after it, has id = -1.
-template <int DM>
+template <int DM, bool PF>
 __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __restrict__ logits, long ld,
                                                                  const SeqCtl* __restrict__ ctl, VocabIds v,
                                                                  const LogitRec* __restrict__ rec, TokOut* __restrict__ cand,
-                                                                 int topk, const uint32_t* __restrict__ deny) {
+                                                                 int topk, const uint32_t* __restrict__ deny,
+                                                                 const float* __restrict__ filt) {
     const int s = blockIdx.x, tid = threadIdx.x, n = v.n_vocab;
     const SeqCtl q = ctl[s];
-    const float* L = logits + (long)s * ld;
+    const float* R = logits + (long)s * ld;
+    const float* L = PF ? filt + (long)s * n : R;
     constexpr int NW = LT / 64;
     __shared__ float shf[NW];
     __shared__ int shi[NW];
@@ -601,7 +654,7 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
 #pragma unroll
     for (int k = NPT_LDS; k < NPT; k++) {
         const int i = tid + k * LT;
-        x.set(k, i < n ? (dl.denied(k) ? -INFINITY : masked_logit(L[i], i, q, v)) : -INFINITY);
+        x.set(k, i < n ? (dl.denied(k) ? -INFINITY : rule_logit<PF>(L[i], i, q, v)) : -INFINITY);
     }
 #pragma unroll
     for (int k0 = 0; k0 < NPT_LDS; k0 += 12) {
@@ -614,11 +667,11 @@ __global__ void __launch_bounds__(LT) logits_topk_combine_kernel(const float* __
 #pragma unroll
         for (int k = 0; k < 12; k++) {
             const int i = tid + (k0 + k) * LT;
-            x.set(k0 + k, i < n ? (dl.denied(k0 + k) ? -INFINITY : masked_logit(t[k], i, q, v)) : -INFINITY);
+            x.set(k0 + k, i < n ? (dl.denied(k0 + k) ? -INFINITY : rule_logit<PF>(t[k], i, q, v)) : -INFINITY);
         }
     }
     if (tid == 0) {
-        const RowRec c = combine_recs<DM>(L, s, q, v, rec, dm);
+        const RowRec c = combine_recs<DM, PF>(L, R, s, q, v, rec, dm);
         s_top[1].tid = c.tid;
         s_top[1].pt = c.pt;
         cand[(long)s * kTopkMax] = c.r;
@@ -674,61 +727,125 @@ static int deny_mode(const uint32_t* deny) {
     return e && atoi(e) > 0 ? 1 : 2;
 }
 
-// logits_kernel by (deny form, grammar on / off, greedy / top-k)
-#define WM_LOGITS_DM_GM(dm, gm, TOPK, ...)                                             \
+// logits_kernel by (deny form, grammar on / off, greedy / top-k, plain / prefiltered)
+#define WM_LOGITS_DM_GM_PF(dm, gm, TOPK, PF, ...)                                      \
     do {                                                                               \
         if (gm) {                                                                      \
-            if (dm == 2) logits_kernel<2, 1, TOPK> __VA_ARGS__;                        \
-            else if (dm == 1) logits_kernel<1, 1, TOPK> __VA_ARGS__;                   \
-            else logits_kernel<0, 1, TOPK> __VA_ARGS__;                                \
+            if (dm == 2) logits_kernel<2, 1, TOPK, PF> __VA_ARGS__;                    \
+            else if (dm == 1) logits_kernel<1, 1, TOPK, PF> __VA_ARGS__;               \
+            else logits_kernel<0, 1, TOPK, PF> __VA_ARGS__;                            \
         } else {                                                                       \
-            if (dm == 2) logits_kernel<2, 0, TOPK> __VA_ARGS__;                        \
-            else if (dm == 1) logits_kernel<1, 0, TOPK> __VA_ARGS__;                   \
-            else logits_kernel<0, 0, TOPK> __VA_ARGS__;                                \
+            if (dm == 2) logits_kernel<2, 0, TOPK, PF> __VA_ARGS__;                    \
+            else if (dm == 1) logits_kernel<1, 0, TOPK, PF> __VA_ARGS__;               \
+            else logits_kernel<0, 0, TOPK, PF> __VA_ARGS__;                            \
         }                                                                              \
+    } while (0)
+#define WM_LOGITS_DM_GM(dm, gm, TOPK, pf, ...)                                         \
+    do {                                                                               \
+        if (pf) WM_LOGITS_DM_GM_PF(dm, gm, TOPK, true, __VA_ARGS__);                   \
+        else WM_LOGITS_DM_GM_PF(dm, gm, TOPK, false, __VA_ARGS__);                     \
+    } while (0)
+// a split-form kernel K<DM, PF> by (the launch has a mask, plain / prefiltered)
+#define WM_LOGITS_SPLIT(K, deny, pf, ...)                                              \
+    do {                                                                               \
+        if (deny) { if (pf) K<1, true> __VA_ARGS__; else K<1, false> __VA_ARGS__; }    \
+        else { if (pf) K<0, true> __VA_ARGS__; else K<0, false> __VA_ARGS__; }         \
     } while (0)
 
 void launch_logits(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* out, float* probs,
-                   void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st) {
+                   void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st,
+                   const float* filtered) {
     if (n_seq <= 0) return;
     if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
+    const bool pf = filtered != nullptr;
     if (!gram && rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
-        if (deny) {
-            logits_part_kernel<1><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny);
-            logits_combine_kernel<1><<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs, deny);
-        } else {
-            logits_part_kernel<0><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, nullptr);
-            logits_combine_kernel<0><<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs, nullptr);
-        }
+        WM_LOGITS_SPLIT(logits_part_kernel, deny, pf, <<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny, filtered));
+        WM_LOGITS_SPLIT(logits_combine_kernel, deny, pf,
+                        <<<n_seq, LT2, 0, st>>>(logits, ld, ctl, v, (const LogitRec*)rec, out, probs, deny, filtered));
         return;
     }
     // (a grammar call always takes the one-workgroup-per-row form: the split form has no second softmax)
     const int dm = deny_mode(deny);
     const size_t lds = row_lds_bytes(dm, v.n_vocab);
-    WM_LOGITS_DM_GM(dm, gram != nullptr, false, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, 1, deny, gram, gram_penalty));
+    WM_LOGITS_DM_GM(dm, gram != nullptr, false, pf,
+                    <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, out, probs, 1, deny, gram, gram_penalty, filtered));
 }
 
 // Top-k after the rules: the form is chosen exactly as launch_logits chooses it for the same n_seq / rec / gram, so
 // candidate 0 of a row is the TokOut launch_logits would return for it.
 void launch_logits_topk(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, TokOut* cand, int k,
-                        void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st) {
+                        void* rec, const uint32_t* deny, const uint32_t* gram, float gram_penalty, hipStream_t st,
+                        const float* filtered) {
     if (n_seq <= 0) return;
     if (k < 1 || k > kTopkMax) WM_FAIL("top-k %d outside 1..%d", k, kTopkMax);
     if (v.n_vocab > NPT * LT) WM_FAIL("vocabulary %d > %d", v.n_vocab, NPT * LT);
+    const bool pf = filtered != nullptr;
     const int dm = deny_mode(deny);
     const size_t lds = row_lds_bytes(dm, v.n_vocab);
     if (!gram && rec && n_seq <= kLogitsSplitMax && v.n_vocab <= 14 * LT2 * KS) {
         const LogitRec* R = (const LogitRec*)rec;
-        if (deny) logits_part_kernel<1><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny);
-        else logits_part_kernel<0><<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, nullptr);
-        if (dm == 2) logits_topk_combine_kernel<2><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny);
-        else if (dm == 1) logits_topk_combine_kernel<1><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny);
-        else logits_topk_combine_kernel<0><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, nullptr);
+        WM_LOGITS_SPLIT(logits_part_kernel, deny, pf, <<<dim3(KS, n_seq), LT2, 0, st>>>(logits, ld, ctl, v, (LogitRec*)rec, deny, filtered));
+        if (pf) {
+            if (dm == 2) logits_topk_combine_kernel<2, true><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny, filtered);
+            else if (dm == 1) logits_topk_combine_kernel<1, true><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny, filtered);
+            else logits_topk_combine_kernel<0, true><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, nullptr, filtered);
+        } else {
+            if (dm == 2) logits_topk_combine_kernel<2, false><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny, nullptr);
+            else if (dm == 1) logits_topk_combine_kernel<1, false><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, deny, nullptr);
+            else logits_topk_combine_kernel<0, false><<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, R, cand, k, nullptr, nullptr);
+        }
         return;
     }
-    WM_LOGITS_DM_GM(dm, gram != nullptr, true, <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, nullptr, k, deny, gram, gram_penalty));
+    WM_LOGITS_DM_GM(dm, gram != nullptr, true, pf,
+                    <<<n_seq, LT, lds, st>>>(logits, ld, ctl, v, cand, nullptr, k, deny, gram, gram_penalty, filtered));
 }
+#undef WM_LOGITS_SPLIT
 #undef WM_LOGITS_DM_GM
+#undef WM_LOGITS_DM_GM_PF
+
+// ---- the stage kernel of whisper_full_params.logits_filter_callback -----------------------------------
+// out[s][i] = pre_logit(logits[s][i]) for the n_seq rows of a step: the row the caller's callback gets. The raw row is
+// left alone (the prefiltered launch reads its no-speech probability from it). HBM-bound at 8 bytes per element. The row
+// stride of `out` is n_vocab, odd for 51865, so a row's first 16-byte boundary moves from row to row: a workgroup-uniform
+// head of 0..3 scalar elements, 16-byte loads and stores from there, a scalar tail; all scalar when the input and the
+// output row are not aligned alike (a caller's ld with another remainder).
+static constexpr int ST = 256;  // threads; 4 elements each
+__global__ void __launch_bounds__(ST) logits_stage_kernel(const float* __restrict__ logits, long ld,
+                                                          const SeqCtl* __restrict__ ctl, VocabIds v, float* __restrict__ out) {
+    const int s = blockIdx.y, n = v.n_vocab;
+    const SeqCtl c = ctl[s];
+    const float* L = logits + (long)s * ld;
+    float* O = out + (long)s * n;
+    const int mis_l = (int)(((uintptr_t)L >> 2) & 3), mis_o = (int)(((uintptr_t)O >> 2) & 3);
+    const int t = blockIdx.x * ST + threadIdx.x;  // the thread's group of 4 along the row
+    if (mis_l != mis_o) {
+        for (int i = 4 * t; i < min(n, 4 * t + 4); i++) O[i] = pre_logit(L[i], i, c, v);
+        return;
+    }
+    const int head = (4 - mis_l) & 3;  // elements before the first 16-byte boundary
+    if (t == 0)
+        for (int i = 0; i < min(head, n); i++) O[i] = pre_logit(L[i], i, c, v);
+    const int i0 = head + 4 * t;
+    if (i0 + 4 <= n) {
+        const float4 x = *(const float4*)(L + i0);
+        float4 y;
+        y.x = pre_logit(x.x, i0, c, v);
+        y.y = pre_logit(x.y, i0 + 1, c, v);
+        y.z = pre_logit(x.z, i0 + 2, c, v);
+        y.w = pre_logit(x.w, i0 + 3, c, v);
+        *(float4*)(O + i0) = y;
+    } else {
+        for (int i = i0; i < n; i++) O[i] = pre_logit(L[i], i, c, v);
+    }
+}
+
+void launch_logits_stage(const float* logits, long ld, const SeqCtl* ctl, int n_seq, const VocabIds& v, float* out,
+                         hipStream_t st) {
+    if (n_seq <= 0) return;
+    if (((uintptr_t)logits | (uintptr_t)out) & 3) WM_FAIL("logits stage: rows not 4-byte aligned");
+    const int groups = (v.n_vocab + 3) / 4 + 1;  // (+1: the head shifts the groups by up to 3 elements)
+    logits_stage_kernel<<<dim3((groups + ST - 1) / ST, n_seq), ST, 0, st>>>(logits, ld, ctl, v, out);
+}
 
 // ---- device-side step advance (pipelined greedy decoding, engine.cpp decode_pipelined) -----------------------
 // After a decode step's logits kernel, in stream order: row r's chosen token becomes its next input and its

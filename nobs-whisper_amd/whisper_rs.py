@@ -112,6 +112,30 @@ class FullParams(C.Structure):
     def set_grammar_penalty(self, penalty: float) -> None:
         self.grammar_penalty = penalty
 
+    # whisper-rs: FullParams::set_filter_logits_callback
+    def set_filter_logits_callback(self, fn) -> None:
+        """fn(tokens, logits): tokens = the row's own sequence of this attempt as a list of TokenData (the prompt is not
+        part of it; [] on the prefill row), logits = a writable float32 numpy view of the row's n_vocab logits after the
+        rules that precede the callback, valid during the call. None: no callback. The trampoline lives as long as this
+        object (or until the next set_filter_logits_callback)."""
+        if fn is None:
+            self._filter_cb = None
+            self.logits_filter_callback = None
+            return
+        import numpy as np
+
+        def tramp(ctx, state, tokens, n_tokens, logits, user_data):
+            n_vocab = lib().whisper_n_vocab(ctx)
+            row = np.ctypeslib.as_array(logits, shape=(n_vocab,))
+            fn([tokens[i] for i in range(n_tokens)], row)
+
+        self._filter_cb = LOGITS_FILTER_CALLBACK(tramp)
+        self.logits_filter_callback = C.cast(self._filter_cb, C.c_void_p)
+
+    # whisper-rs: FullParams::set_tdrz_enable
+    def set_tdrz_enable(self, on: bool) -> None:
+        self.tdrz_enable = on
+
 
 VAD_ERR = -11     # whisper_full* with vad set: vad_model_path is null, unreadable or refused (whisper.h)
 GRAMMAR_ERR = -9  # whisper_full*: the grammar is malformed or left-recursive (whisper.h)
@@ -142,6 +166,12 @@ class GrammarStats(C.Structure):
 class TokenData(C.Structure):
     _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("plog", C.c_float), ("pt", C.c_float),
                 ("ptsum", C.c_float), ("t0", C.c_int64), ("t1", C.c_int64), ("t_dtw", C.c_int64), ("vlen", C.c_float)]
+
+
+# whisper_logits_filter_callback (include/whisper.h)
+LOGITS_FILTER_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(TokenData), C.c_int, C.POINTER(C.c_float),
+                                     C.c_void_p)
+KSTAT_LOGITS_STAGE = 105  # WHISPER_MI355X_KSTAT_LOGITS_STAGE; kernel-timing class 18
 
 
 class WindowDecision(C.Structure):
@@ -264,6 +294,14 @@ def lib() -> C.CDLL:
         "whisper_mi355x_batch_segment_t1": (C.c_int64, [vp, C.c_int, C.c_int]),
         "whisper_mi355x_batch_segment_n_tokens": (C.c_int, [vp, C.c_int, C.c_int]),
         "whisper_mi355x_batch_token_data": (TokenData, [vp, C.c_int, C.c_int, C.c_int]),
+        "whisper_mi355x_batch_segment_speaker_turn_next": (C.c_bool, [vp, C.c_int, C.c_int]),
+        "whisper_full_get_segment_speaker_turn_next_from_state": (C.c_bool, [vp, C.c_int]),
+        "whisper_full_get_segment_speaker_turn_next": (C.c_bool, [vp, C.c_int]),
+        "whisper_mi355x_debug_logits_stage": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, vp]),
+        "whisper_mi355x_debug_logits_ex": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, C.c_int,
+                                                     C.POINTER(Cand), fp]),
+        "whisper_mi355x_debug_logits_topk_ex": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(SeqCtl), C.c_int, C.c_int, C.c_int,
+                                                          C.POINTER(Cand), C.POINTER(Cand)]),
         "whisper_mi355x_batch_lang_id": (C.c_int, [vp, C.c_int]),
         "whisper_mi355x_batch_decoded_tokens": (C.c_long, [vp]),
         "whisper_mi355x_window_decisions": (C.c_int, [vp, C.c_int, C.POINTER(WindowDecision), C.c_int]),
@@ -427,6 +465,7 @@ class Segment:
     t1: int
     text: bytes
     tokens: list
+    speaker_turn_next: bool = False  # whisper_full_params.tdrz_enable (whisper_full_get_segment_speaker_turn_next)
 
 
 def reference_full_params(language: str | None = "en", initial_prompt: str | None = None) -> FullParams:
@@ -732,7 +771,8 @@ class WhisperState:
             toks.append((d.id, d.tid, d.p, d.plog))
         return Segment(L.whisper_full_get_segment_t0_from_state(self.ptr, i),
                        L.whisper_full_get_segment_t1_from_state(self.ptr, i),
-                       L.whisper_full_get_segment_text_from_state(self.ptr, i), toks)
+                       L.whisper_full_get_segment_text_from_state(self.ptr, i), toks,
+                       bool(L.whisper_full_get_segment_speaker_turn_next_from_state(self.ptr, i)))
 
     def segments(self) -> list:
         return [self.get_segment(i) for i in range(self.full_n_segments())]
@@ -790,8 +830,16 @@ class WhisperState:
                 toks.append((d.id, d.tid, d.p, d.plog))
             out.append(Segment(L.whisper_mi355x_batch_segment_t0(self.ptr, job, i),
                                L.whisper_mi355x_batch_segment_t1(self.ptr, job, i),
-                               L.whisper_mi355x_batch_segment_text(self.ptr, job, i), toks))
+                               L.whisper_mi355x_batch_segment_text(self.ptr, job, i), toks,
+                               bool(L.whisper_mi355x_batch_segment_speaker_turn_next(self.ptr, job, i))))
         return out
+
+    def logits_stage_stats(self) -> tuple:
+        """WHISPER_MI355X_KSTAT_LOGITS_STAGE: (ms, launches, bytes) of the stage kernel of calls with a
+        logits_filter_callback; zeros unless class 18 is timed."""
+        out = (C.c_double * 3)()
+        assert self.L.whisper_mi355x_kernel_stats(self.ptr, KSTAT_LOGITS_STAGE, out) == 0
+        return out[0], int(out[1]), out[2]
 
     def vad_ms(self) -> float:
         """whisper_mi355x_vad_ms: wall time of the VAD filter step of the last call (0 with vad off)."""
